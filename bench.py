@@ -16,8 +16,16 @@ Online VB (BASELINE config 5, `-method vb`): python bench.py --method vb
   (one rank each, every case of those users local) and the item rows' sums
   are all-gathered per pass (RCCL); the dataset is fixed, so scaling is strong.
 
-Single GPU:  python bench.py [--steps K --warmup W]
-Multi GPU:   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
+Single GPU:  python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]
+  a plain run sets up, warms up, times the K steps and prints the result line
+  (a learner runs at most CHAIN_SWEEPS sweeps, before the reference chain's
+  collapse: a longer run goes on, clock stopped meanwhile, on a fresh learner);
+  --full adds the legs beside the headline: the f32 measurement, time-to-RMSE,
+  load timing, each launch kind's standalone rate and the CPU baseline.
+  --dump-outputs DIR writes the timed learner's state after its last step
+  (factors, test predictions, hyperparameters, the timed steps' RMSE) as
+  DIR/<name>.npy; inputs and seeds are fixed, so two builds compare file by file.
+Multi GPU:  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
   one process per GPU; users/items are row-block partitioned (nnz balanced)
   and the fresh U / V blocks are exchanged with RCCL (grouped in-place
   broadcasts over xGMI) between half-sweeps, the cross-rank residuals with a
@@ -49,6 +57,14 @@ def parse():
                     help="mcmc: SBPMF Gibbs (headline); vb: online VB; libfm / als: libFM's own MCMC chain / ALS")
     ap.add_argument("--shape", default=None, help="ml-20m (mcmc default) | netflix (vb default) | ml-1m | ...")
     ap.add_argument("--K", type=int, default=None, help="factors (default 100 mcmc / 200 vb)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the f32 measurement, time-to-RMSE, load "
+                         "timing, every launch kind's standalone time and the CPU baseline (each can be dropped "
+                         "again with its --no-* option); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed learner holds after its last step (factors, "
+                         "test predictions, hyperparameters, the timed steps' RMSE) as DIR/<name>.npy (float64; "
+                         "large arrays as a fixed seeded sample of rows, under 64 MB in all)")
     ap.add_argument("--precision", default="f64")
     ap.add_argument("--quirks", default="final",
                     help="final (gibbs_sbpmf_final.cpp, headline) | bias2 (the biased sampler of the top-level "
@@ -138,48 +154,117 @@ def make_learner(args, world, rank, local, precision, comm):
     return L, Data
 
 
-def measure(args, world, rank, local, precision, train, test, comm):
-    L, Data = make_learner(args, world, rank, local, precision, comm)
-    t0 = time.time()
-    L.set_data(Data(*train), Data(*test))
-    prep_s = time.time() - t0
-    for _ in range(args.warmup):
-        L.learn(sweeps=1)
-    barrier(world)
-    device_sync()
-    t0 = time.perf_counter()
+DUMP_BUDGET = 60_000_000  # bytes of .npy payload per --dump-outputs directory
+DUMP_SEED = 2015          # of the row sample taken from arrays that do not fit whole
+
+
+def learner_outputs(L, hist, biased):
+    """What a caller of the timed learner receives after its last step, as float64 arrays;
+    hist: the timed steps' per-step records."""
+    U, V = L.factors()
+    out = {"U": U, "V": V, "predict": L.predict()}
+    if biased:
+        bu, bv, b0 = L.biases()
+        out.update({"bias_user": bu, "bias_item": bv, "bias_0": np.array([b0])})
+    h = L.hyper()
+    out.update({k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in h.items()})
+    out["rmse_avg"] = np.array([r["rmse_avg"] for r in hist], dtype=np.float64)
+    out["rmse_this"] = np.array([r["rmse_this"] for r in hist], dtype=np.float64)
+    return out
+
+
+def dump_outputs(dirpath, arrays):
+    """DIR/<name>.npy for every array; arrays below 1 MB whole, the others share the rest of
+    DUMP_BUDGET evenly, each as its first-axis rows at a sorted sample drawn with DUMP_SEED
+    (the same rows for the same shapes, so two builds' files compare row for row)."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    big = [k for k, a in arrays.items() if a.nbytes > (1 << 20)]
+    small = sum(a.nbytes for k, a in arrays.items() if k not in big)
+    cap = (DUMP_BUDGET - small) // max(len(big), 1)
+    rng = np.random.default_rng(DUMP_SEED)
+    for k, a in arrays.items():
+        if k in big and a.nbytes > cap:
+            rows = max(1, cap // (a.nbytes // a.shape[0]))
+            a = a[np.sort(rng.choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+
+
+# Sweeps one learner runs before the benchmark replaces it with a fresh one.  The headline
+# sampler restates the reference's chain, which uses the posterior variance as the stdev and
+# on the ML-20M-shaped set collapses from sweep 28 (tau -> 0 -> NaN, DESIGN.md §6); a step
+# is a sweep of the live sampler, so no learner is driven that far, whatever --steps asks for.
+CHAIN_SWEEPS = 24
+
+
+def measure(args, world, rank, local, precision, train, test, comm, dump=False):
+    """W warm-up sweeps, then N timed ones.  A learner runs at most CHAIN_SWEEPS sweeps: when
+    it has, the clock stops, a fresh learner (same seed and data: the same chain again) takes
+    over after one warm-up sweep of its own, and the clock goes on.  With W + N <= CHAIN_SWEEPS
+    (the default 3 + 20) that is one learner and one timed run."""
     from sbmf._lib import NKIND
+    KS = list(_lib_kind_names()).index("gres_stage")
     kern_ms = np.zeros((2, NKIND))
+    stream_ms = np.zeros(2)
+    cur = {}
 
     # each sweep's streaming-kind times (HIP events), read from the callback; the other kinds are
-    # timed on a run's first sweep only (their values then stay), so they are read once below
-    KS = list(_lib_kind_names()).index("gres_stage")
-    stream_ms = np.zeros(2)
-
+    # timed on a run's first sweep only (their values then stay), so they are read once per run
     def per_sweep(_rec):
-        t = L.timing()
+        t = cur["L"].timing()
         stream_ms[0] += t.kern_ms[0][KS]
         stream_ms[1] += t.kern_ms[1][KS]
         return False
 
-    # one run of K sweeps (sweep s+1's start is queued at the end of sweep s; the Gram-block
-    # kinds are timed on the run's first sweep, the streaming kind on every sweep)
-    L.learn(sweeps=args.steps, callback=per_sweep)
-    device_sync()
-    barrier(world)
-    dt = time.perf_counter() - t0
+    def fresh(warm):
+        L, Data = make_learner(args, world, rank, local, precision, comm)
+        t0 = time.time()
+        L.set_data(Data(*train), Data(*test))
+        prep = time.time() - t0
+        for _ in range(warm):
+            L.learn(sweeps=1)
+        cur["L"] = L
+        return L, prep
+
+    used = min(args.warmup, CHAIN_SWEEPS)  # a longer warm-up would only run the first learner out
+    L, prep_s = fresh(used)
+    left, dt, learners, sweeps_run, hist = args.steps, 0.0, 1, 0, []
+    while left:
+        if used >= CHAIN_SWEEPS:
+            sweeps_run += len(L.history)
+            L.close()
+            L, _ = fresh(1)
+            used, learners = 1, learners + 1
+        n = min(left, CHAIN_SWEEPS - used)
+        barrier(world)
+        device_sync()
+        t0 = time.perf_counter()
+        # one run of n sweeps (sweep s+1's start is queued at the end of sweep s; the Gram-block
+        # kinds are timed on the run's first sweep, the streaming kind on every sweep)
+        L.learn(sweeps=n, callback=per_sweep)
+        device_sync()
+        barrier(world)
+        dt += time.perf_counter() - t0
+        t = L.timing()
+        kern_ms += np.array([[t.kern_ms[s][k] for k in range(NKIND)] for s in range(2)]) * n
+        hist += L.history[-n:]
+        used, left = used + n, left - n
     dt = max_over_ranks(world, dt)
     t = L.timing()
-    kern_ms[:] = np.array([[t.kern_ms[s][k] for k in range(NKIND)] for s in range(2)]) * args.steps
     kern_ms[:, KS] = stream_ms
     kbytes = np.array([[t.kern_bytes[s][k] for k in range(NKIND)] for s in range(2)], dtype=np.float64)
     krows = np.array([[t.kern_rows[s][k] for k in range(NKIND)] for s in range(2)])
     res = {
         "seconds": dt, "prep_s": prep_s, "kern_ms": kern_ms / args.steps, "kern_bytes": kbytes, "kern_rows": krows,
         "bytes_alg": t.bytes_algorithmic, "rmse": L.history[-1]["rmse_avg"],
-        "sweeps_run": len(L.history), "ms_user": t.ms_user_half, "ms_item": t.ms_item_half, "ms_hyper": t.ms_hyper,
+        "sweeps_run": sweeps_run + len(L.history), "learners": learners,
+        "ms_user": t.ms_user_half, "ms_item": t.ms_item_half, "ms_hyper": t.ms_hyper,
         "ms_eval": t.ms_eval, "ms_comm": t.ms_comm,
     }
+    if dump:  # after the clock has stopped; every rank reads (predict exchanges its ranges), rank 0 writes
+        outs = learner_outputs(L, hist, args.quirks.startswith("bias"))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     L.close()
     return res
 
@@ -466,6 +551,10 @@ def vb_main(args):
                      "epoch_aggregate": {"kernels": "every VB kernel of the epoch", "bytes": bytes_epoch,
                                          "ms": gpu_ms, "frac": bytes_epoch / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}},
     }
+    if args.dump_outputs:
+        outs = learner_outputs(L, L.history[-args.steps:], True)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     L.close()
     if not args.no_cpu and rank == 0 and world == 1:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
@@ -575,6 +664,10 @@ def libfm_main(args):
                      "frac": bytes_it / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                      "bytes_per_iter": bytes_it},
     }
+    if args.dump_outputs:
+        outs = learner_outputs(L, L.history[-args.steps:], True)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     L.close()
     if not args.no_cpu and rank == 0 and world == 1:
         out["cpu_baseline"] = libfm_cpu_baseline(train, test, dims, K, als, args.cpu_seconds)
@@ -591,6 +684,8 @@ def libfm_main(args):
 
 def main():
     args = parse()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_f32 = args.no_cpu = args.no_ttr = args.no_load = True
     if args.method in ("libfm", "als"):
         if args.shape is None:
             args.shape = "ml-20m"
@@ -610,7 +705,7 @@ def main():
     KIND_STREAM_IDX = list(KIND_NAMES).index("gres_stage")
     train, test, dims = synth.generate(args.shape)
     comm = mk_comm(world, rank, local)  # one communicator for every leg below
-    main_res = measure(args, world, rank, local, args.precision, train, test, comm)
+    main_res = measure(args, world, rank, local, args.precision, train, test, comm, dump=bool(args.dump_outputs))
     if args.quirks != "final":  # the extra legs (f32, time-to-RMSE, loads) belong to the headline sampler
         args.no_f32 = args.no_ttr = args.no_load = True
     f32 = None
@@ -665,7 +760,7 @@ def main():
     # 124 MB U table (6.3 TB/s; profiles/r01_gather_ceiling.txt), both quoted as fractions of the
     # 8 TB/s spec too.  The default schedule's per-kind windows are reported beside them, without a
     # rate: a kind waiting for CU slots beside the persistent streaming launch spans that wait too.
-    solo = standalone_kinds(args, local, train, test) if world == 1 else None
+    solo = standalone_kinds(args, local, train, test) if world == 1 and args.full else None
     ceil = {0: 8100.0, 1: 6300.0}
     bins = {}
     for s_ in range(2):
@@ -704,6 +799,7 @@ def main():
                    "K": args.K, "rng": "philox", "quirks": args.quirks,
                    "parallelism": "rows x%d (%s)" % (world, "host-shm exchange, testing only" if os.environ.get("SBMF_COMM") == "host" else "RCCL block broadcast + p2p residual exchange"),
                    "test_rmse_after": main_res["rmse"], "sweeps_run": main_res["sweeps_run"],
+                   "learners": main_res["learners"], "sweeps_per_learner": CHAIN_SWEEPS,
                    "prepare_s": main_res["prep_s"], "load": loads,
                    "time_to_test_rmse_0.85": ttr,
                    "ms_user_half": main_res["ms_user"], "ms_item_half": main_res["ms_item"],
@@ -719,7 +815,7 @@ def main():
                      "sweep_alg_GBs": main_res["bytes_alg"] / (main_res["seconds"] / args.steps) / 1e9,
                      "bins": bins,
                      "bins_note": "rates from each kind's standalone device time (serial schedule, tune bit 29, "
-                     "measured in this run); ms_default_window is the kind's start-to-end span in the default "
+                     "measured in a --full run); ms_default_window is the kind's start-to-end span in the default "
                      "schedule, where a half's Gram-block launches run on two side streams beside its "
                      "streaming launch (overlapped: no rate)",
                      "bins_kernels": "bins are row-length classes; by default (f64) gblock_w16 (9-64 ratings) and "

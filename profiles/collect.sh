@@ -1,6 +1,6 @@
 #!/bin/bash
 # One measurement pass on a 1-GPU MI355X box (run from the repo root via gpurun):
-#   bash profiles/collect.sh <tag> bench   default bench line (f64 + f32 + CPU baseline + time-to-RMSE)
+#   bash profiles/collect.sh <tag> bench   bench.py --full line (f64 + f32 + CPU baseline + time-to-RMSE)
 #   bash profiles/collect.sh <tag> trace   rocprofv3 --kernel-trace --stats of a bench run
 #   bash profiles/collect.sh <tag> fetch   --pmc FETCH_SIZE      (each counter pass on its own,
 #   bash profiles/collect.sh <tag> write   --pmc WRITE_SIZE       never combined with other
@@ -21,7 +21,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="$R/bench.py"
 SHORT="--no-cpu --no-f32 --no-ttr --no-load ${BENCH_ARGS:-}"  # BENCH_ARGS: e.g. "--shape ml-10m --K 100"
 case "$PASS" in
-  bench) timeout -k 10 500 python3 "$BENCH" ${BENCH_ARGS:-} > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" ;;
+  bench) timeout -k 10 500 python3 "$BENCH" --full ${BENCH_ARGS:-} > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" ;;
   trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${TAG}_trace" -o "$TAG" -- \
            python3 "$BENCH" --steps 10 --warmup 2 $SHORT > "$O/${TAG}_trace.log" 2>&1 ;;
   fetch) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d "$O/${TAG}_pmc_fetch" -o "$TAG" -- \
