@@ -57,10 +57,13 @@ hipError_t launch_gblock_nw(int nw, const uint32_t* rows, uint32_t nrows, const 
 template <typename T>
 hipError_t launch_gblock(int kind, const uint32_t* rows, uint32_t nrows, const HalfArgs<T>& a, hipStream_t st);
 
+template <typename T>
+struct GresCold;  // the streaming row kernels' cold arguments, below
 // Whole rows of a Gram-block bin on the streaming kernel's code (k_grow), one workgroup of
 // nw (1 or 2) waves per row: rows of at most grow_maxdeg(nw, f64) ratings.
 template <typename T>
-hipError_t launch_grow(int nw, const uint32_t* rows, uint32_t nrows, const HalfArgs<T>& a, hipStream_t st);
+hipError_t launch_grow(int nw, const uint32_t* rows, uint32_t nrows, const HalfArgs<T>& a, const GresCold<T>* d_cold,
+                       hipStream_t st);
 uint32_t grow_maxdeg(int nw, bool f64);
 
 // Streaming-kernel task: at most `cmax` ratings of one row (the whole row,
@@ -74,8 +77,14 @@ struct SplitTask {
     uint32_t chunk;  // chunk index within the row
     uint32_t slab0;  // split rows: first chunk slab of the row (also its new-own slot)
     uint32_t cnt0;   // split rows: first block counter of the row
-    uint32_t pad;
+    // split rows, byte offsets in the set's slab area (the host checks the area is < 2^32 bytes),
+    // so the exchange addresses are the slab base plus 32-bit offsets:
+    uint32_t xrow;   // block 0 of the row's first chunk
+    uint32_t xown;   // block 0 of this chunk: xrow + chunk * xstr
+    uint32_t xstr;   // from one chunk's slabs to the next's: nblk * SLAB_DOUBLES * 8
+    uint32_t pad[2];
 };
+constexpr uint32_t SLAB_DOUBLES = 16 * 16 + 16;  // per (chunk, block): 16x16 image | c
 struct SplitRow {
     uint32_t row, slab0, nch, pad;
 };
@@ -93,6 +102,41 @@ struct SplitSync {
     uint64_t lim_slab;   // doubles of `slabs` (CHECK=1 builds)
     uint32_t lim_chunk;  // entries of chunk_sq / chunk_tr (and rows of newown)
 };
+// The streaming row kernels' (k_gres, k_grow) cold arguments: everything their k-block loop does
+// not read.  One block per (side, launch shape) lives in device memory; the kernels read its
+// fields with scalar loads where they use them (task staging, the epilogue), so they hold no
+// registers across the block loop.  No field may depend on the stage or the sweep: the host
+// uploads a block only when it changes (cold_block, sbmf.cpp).  The block loop's own arguments are passed by value
+// (GresHot, kernels.hip), built by the launchers from HalfArgs / SplitSync.
+template <typename T>
+struct GresCold {
+    const uint32_t* ptr;
+    const uint32_t* part;
+    const uint32_t* perm;
+    const T* E_this;
+    T* E_other;
+    const T* r_this;
+    T* own;
+    const T* zbuf;
+    const T* sig;        // [sig | mu], mu = sig + Kp
+    double* row_sq;
+    double* row_tr;
+    double* chunk_sq;    // split rows (k_gres)
+    double* chunk_tr;
+    T* newown;
+    T lo, hi;
+    uint32_t zrow;
+    int e_from_dot;
+    // diagnostic builds only (KPROF=1: prof; CHECK=1: the extents)
+    unsigned long long* prof;
+    uint64_t lim_partner, lim_other, lim_this, lim_slab;
+    uint32_t lim_rows, lim_chunk;
+};
+// The cold block of a launch with these arguments (sy: null for k_grow).  HalfArgs::mu must be
+// sig + Kp (one table).
+template <typename T>
+GresCold<T> gres_cold(const HalfArgs<T>& a, const SplitSync* sy);
+
 // Task capacity (ratings) of the streaming kernel k_gres for the variant `tune`:
 // 4 * waves * vectors-per-wave, the partner slices held in VGPRs.
 template <typename T>
@@ -108,10 +152,11 @@ int gstream_blocks_per_cu(uint32_t cmax, uint32_t tune);
 // a chunk only waits for peers that the next free workgroups claim.  Split rows
 // are then published by k_split_finish.  sy.counters[0..ncounters] must be zero
 // when the launch starts: sbmf.cpp clears every set's counters with one memset
-// per half, ahead of the half's launches.
+// per half, ahead of the half's launches.  d_cold: gres_cold(a, &sy) in device memory, valid
+// until the launch has run.
 template <typename T>
 hipError_t launch_gstream(const SplitTask* tasks, uint32_t ntask, uint32_t grid, const SplitRow* srows, uint32_t nsrow,
-                          const HalfArgs<T>& a, const SplitSync& sy, hipStream_t st);
+                          const HalfArgs<T>& a, const SplitSync& sy, const GresCold<T>* d_cold, hipStream_t st);
 
 // Full residual recompute over rows [r0, r1) of one orientation, split into
 // tasks of <= RESID_CHUNK ratings (one wave each): e = r - own.partner is

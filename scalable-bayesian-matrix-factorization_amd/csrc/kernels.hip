@@ -36,11 +36,11 @@
 // build never includes it.
 //   CHK(i, extent)           a global index (CHECK=1: validated, printed, redirected)
 //   SBMF_GBLOCK_PHASES(on)   declares stamp(phase) in k_gblock (KPROF=1: wave 0's
-//   SBMF_GRES_PHASES(nch)    cycles per phase) / in k_gres' task loop
+//   SBMF_GRES_PHASES(nch, p) cycles per phase) / in k_gres' task loop
 #ifndef SBMF_KERNELS_INSTR_H_
 #define CHK(i, lim) (i)
 #define SBMF_GBLOCK_PHASES(on) auto stamp = [](int) {}
-#define SBMF_GRES_PHASES(nch) auto stamp = [](int) {}
+#define SBMF_GRES_PHASES(nch, prof_) auto stamp = [](int) {}
 #endif
 
 namespace sbmf {
@@ -666,6 +666,41 @@ template <typename T>
 struct GresW {  // vectors (of 4 ratings) per wave held in VGPRs: 64 VGPRs of slices
     static constexpr int VW = sizeof(T) == 8 ? 32 : 64;
 };
+// The arguments the k-block loop reads, by value: 16 dwords for k_gres (with its task list and
+// count 19 of the 102 usable SGPRs), against the 80 of HalfArgs + SplitSync, which the kernels
+// kept in SGPRs across the persistent task loop and spilled to VGPR lanes.
+// Everything else is GresCold (kernels.h), read where it is used.
+template <typename T>
+struct GresHot {
+    const T* partner;       // [P+2][Kp]
+    const GresCold<T>* cold;
+    T* own;                 // k_grow (DIRECT) only: the solving wave writes the row itself
+    const T* sig;           // k_grow at KL = 256 (SMG) only: [sig | mu] read per block
+    double* slabs;          // k_gres: the set's slab area
+    uint32_t* counters;     // k_gres: block counters, then the queue head at [ncounters]
+    uint32_t* timeout;
+    T tau;
+    uint32_t K, Kp;
+    uint32_t ncounters;
+    int sd_is_var;
+};
+// The cold block as constant memory behind a compiler barrier: loads through the returned pointer
+// are scalar and cannot move above this point, so a field read in task staging or in the epilogue
+// holds no register across the block loop.  (Without the barrier the compiler hoists every load
+// to the kernel's entry and spills it again: worse than the by-value block.)
+template <typename T>
+using ColdP = const __attribute__((address_space(4))) GresCold<T>*;
+template <typename T>
+__device__ __forceinline__ ColdP<T> cold_here(const GresCold<T>* p) {
+    ColdP<T> q = (ColdP<T>)(uintptr_t)p;
+    asm volatile("" : "+s"(q));
+    return q;
+}
+// a pointer read from the cold block, as a global-memory pointer (not a flat one)
+template <typename U>
+__device__ __forceinline__ __attribute__((address_space(1))) U* glob(U* p) {
+    return (__attribute__((address_space(1))) U*)(uintptr_t)p;
+}
 // LIST: whole rows of a Gram-block bin, one workgroup per row of the list (k_grow; NW 1 or 2,
 // no split rows), instead of tasks claimed from a queue (k_gres).  One wave (NW = 1) takes
 // its G_B straight from the MFMA registers into the solve's image and its D from its own
@@ -673,7 +708,7 @@ struct GresW {  // vectors (of 4 ratings) per wave held in VGPRs: 64 VGPRs of sl
 // one-wave workgroups per SIMD.
 template <typename T, int NW, int SIDE, bool LIST, int KL = 256>
 __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, const uint32_t* __restrict__ lrows,
-                                         uint32_t ntask, const HalfArgs<T>& a, const SplitSync& sy) {
+                                         uint32_t ntask, const GresHot<T>& a) {
     typedef typename MfmaT<T>::acc_t acc_t;
     constexpr bool ONE = NW == 1;
     // whole rows of a list: the solving waves write the new own row themselves; KL (>= Kp) sizes
@@ -685,6 +720,7 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
     constexpr int VW = GresW<T>::VW;
     constexpr uint32_t CAP = 4 * NW * VW;
     constexpr int SL = GB * GB + GB;  // slab doubles per (chunk, block): 16x16 image (lower + diagonal) | c
+    static_assert(SL == (int)SLAB_DOUBLES, "the host's exchange offsets (SplitTask::xrow, xstr) use SLAB_DOUBLES");
     const int lane = threadIdx.x & 63;
     const int wr = threadIdx.x >> 6;
     const int ci = lane & 15;
@@ -692,6 +728,9 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
     const uint32_t K = a.K, Kp = a.Kp;
     const uint32_t nblk = (K + GB - 1) / GB;
     const T tau = a.tau;
+#ifdef SBMF_KPROF_BUILD
+    unsigned long long* const kprof_ = cold_here(a.cold)->prof;
+#endif
     __shared__ uint32_t pjL[CAP];      // partner row offset (row * Kp) per rating slot (zero row past the end)
     __shared__ uint32_t pmL[CAP];      // residual scatter target per rating
     __shared__ T eL[CAP];              // residuals (bit-identical in the 16 lanes of a rating)
@@ -729,10 +768,12 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
     // this wave's index as a scalar, and the lane: the thread id is rebuilt from them in the
     // block loop (no VGPR held across it, no spill slot to reload)
     const int wr_s = __builtin_amdgcn_readfirstlane(wr);
-    if constexpr (!SMG)
-    for (uint32_t k = threadIdx.x; k < Kp; k += 64 * NW) {
-        sgL[k] = a.sig[k];
-        muL[k] = a.mu[k];
+    if constexpr (!SMG) {
+        const auto sg = glob(cold_here(a.cold)->sig);
+        for (uint32_t k = threadIdx.x; k < Kp; k += 64 * NW) {
+            sgL[k] = sg[k];
+            muL[k] = sg[Kp + k];
+        }
     }
     // this lane's slots: vector j of wave wr is rating 4*(wr + j*NW) + rr, i.e.
     // a fixed per-lane base plus j*4*NW (an immediate LDS offset)
@@ -755,57 +796,94 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
             if (it > 0 || ti >= ntask) break;
         } else {
             if (threadIdx.x == 0)
-                qti = __hip_atomic_fetch_add(sy.counters + sy.ncounters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                qti = __hip_atomic_fetch_add(a.counters + a.ncounters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
-            ti = qti;
+            ti = __builtin_amdgcn_readfirstlane(qti);  // uniform: the task record by scalar loads
             __syncthreads();  // every thread has its ticket before thread 0 claims the next
             if (ti >= ntask) break;
         }
-        SplitTask tk;
-        if constexpr (LIST) {
-            const uint32_t r = lrows[ti];
-            tk = SplitTask{r, a.ptr[r], a.ptr[r + 1] - a.ptr[r], 1u, 0u, 0u, 0u, 0u};
-        } else {
-            tk = tasks[ti];
+        // The task's fields the block loop reads: the chunk count and, for split rows, the
+        // host-computed 32-bit offsets of the exchange (no 64-bit slab arithmetic per block).
+        // Everything else of the task (row, range, chunk, slot) is read where it is used, from
+        // the task record behind a compiler barrier, like the cold block.
+        auto task_here = [&]() -> SplitTask {
+            if constexpr (LIST) {
+                auto lr = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(lrows + ti);
+                asm volatile("" : "+s"(lr));
+                const uint32_t r = *lr;
+                const auto rp = glob(cold_here(a.cold)->ptr);
+                const uint32_t b = rp[r];
+                return SplitTask{r, b, rp[r + 1] - b, 1u, 0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+            } else {
+                auto tq = (const __attribute__((address_space(4))) SplitTask*)(uintptr_t)(tasks + ti);
+                asm volatile("" : "+s"(tq));
+                return SplitTask{tq->row,  tq->beg,  tq->len,  tq->nch,  tq->chunk, tq->slab0,
+                                 tq->cnt0, tq->xrow, tq->xown, tq->xstr, {0u, 0u}};
+            }
+        };
+        uint32_t n, nch, xrow = 0, xown = 0, xstr = 0, cnt0 = 0;
+        {
+            const SplitTask tk = task_here();
+            n = tk.len;
+            nch = tk.nch;
+            if constexpr (!LIST) {
+                xrow = tk.xrow;
+                xown = tk.xown;
+                xstr = tk.xstr;
+                cnt0 = tk.cnt0;
+            }
         }
-        const uint32_t n = tk.len;
         if (n == 0) continue;  // empty round slot (uniform)
-        const uint32_t row = tk.row, beg = tk.beg, nch = tk.nch;
         const uint32_t vpw = ((n + 3) / 4 + NW - 1) / NW;  // vectors per wave
-        SBMF_GRES_PHASES(nch);  // stamp(phase): the diagnostic phase profile
+        SBMF_GRES_PHASES(nch, kprof_);  // stamp(phase): the diagnostic phase profile
         // size class: the task's vectors per wave, rounded up to VW/4, VW/2, 3VW/4 or VW
         auto body = [&](auto vc) {
             constexpr int VC = decltype(vc)::value;
             const uint32_t npad = 4 * NW * VC;
-            for (uint32_t x = threadIdx.x; x < npad; x += 64 * NW) {
-                const bool in = x < n;
-                const uint32_t qx = in ? (uint32_t)CHK(beg + x, a.lim_this) : 0u;
-                pjL[x] = (in ? a.part[qx] : a.zrow) * Kp;  // host checks (P+2)*Kp < 2^32
-                pmL[x] = in ? a.perm[qx] : 0u;
-                if (!a.e_from_dot) eL[x] = in ? a.E_this[qx] : T(0);
-            }
-            for (uint32_t k = threadIdx.x; k < Kp; k += 64 * NW) {  // per-half normals and old values of the row
-                zL[k] = k < K ? a.zbuf[(size_t)CHK(row, a.lim_rows) * K + k] : T(0);
-                oL[k] = a.own[(size_t)CHK(row, a.lim_rows) * Kp + k];  // padding columns are zero
-            }
-            __syncthreads();
-            if (a.e_from_dot) {  // validation mode (tune bit 1): e0 = r - own.partner
-                for (uint32_t v = wr; v < (npad >> 2); v += NW) {
-                    const uint32_t q = 4 * v + rr;
-                    const uint32_t pj = pjL[q];
-                    T d = T(0);
-                    for (uint32_t k0 = 0; k0 < K; k0 += GB)
-                        d += a.partner[(size_t)pj + k0 + ci] * a.own[(size_t)row * Kp + k0 + ci];
-                    d = row16_sum(d);
-                    if (ci == 0) eL[q] = q < n ? a.r_this[beg + q] - d : T(0);
+            uint32_t row_d = 0;  // DIRECT: the row, for the solving wave's writes
+            {  // ---- staging: the cold block and the task record, read here
+                const ColdP<T> cs = cold_here(a.cold);
+                const SplitTask tk = task_here();
+                const uint32_t row = tk.row, beg = tk.beg;
+                if constexpr (DIRECT) row_d = row;
+                const bool efd = cs->e_from_dot != 0;
+                const auto part = glob(cs->part);
+                const auto perm = glob(cs->perm);
+                const auto Et = glob(cs->E_this);
+                const uint32_t zrow = cs->zrow;
+                for (uint32_t x = threadIdx.x; x < npad; x += 64 * NW) {
+                    const bool in = x < n;
+                    const uint32_t qx = in ? (uint32_t)CHK(beg + x, cs->lim_this) : 0u;
+                    pjL[x] = (in ? part[qx] : zrow) * Kp;  // host checks (P+2)*Kp < 2^32
+                    pmL[x] = in ? perm[qx] : 0u;
+                    if (!efd) eL[x] = in ? Et[qx] : T(0);
+                }
+                const auto zb = glob(cs->zbuf);
+                const auto ow = glob(cs->own);
+                for (uint32_t k = threadIdx.x; k < Kp; k += 64 * NW) {  // per-half normals and old values of the row
+                    zL[k] = k < K ? zb[(size_t)CHK(row, cs->lim_rows) * K + k] : T(0);
+                    oL[k] = ow[(size_t)CHK(row, cs->lim_rows) * Kp + k];  // padding columns are zero
                 }
                 __syncthreads();
+                if (efd) {  // validation mode (tune bit 1): e0 = r - own.partner
+                    const auto rt = glob(cs->r_this);
+                    for (uint32_t v = wr; v < (npad >> 2); v += NW) {
+                        const uint32_t q = 4 * v + rr;
+                        const uint32_t pj = pjL[q];
+                        T d = T(0);
+                        for (uint32_t k0 = 0; k0 < K; k0 += GB)
+                            d += a.partner[(size_t)pj + k0 + ci] * ow[(size_t)row * Kp + k0 + ci];
+                        d = row16_sum(d);
+                        if (ci == 0) eL[q] = q < n ? rt[beg + q] - d : T(0);
+                    }
+                    __syncthreads();
+                }
             }
             stamp(0);  // staging
             const T* __restrict__ pbase = a.partner + ci;
             // the gather of vector j's slice of block t
             auto gat = [&](int j, uint32_t t) -> T {
-                return pbase[CHK((size_t)pjW[j * JS] + t * GB + ci, a.lim_partner) - ci];
+                return pbase[CHK((size_t)pjW[j * JS] + t * GB + ci, cold_here(a.cold)->lim_partner) - ci];
             };
             // Residual update e_v -= S_v D (vector v: 4 ratings x 16 columns, lane ci
             // holding column ci): s_v *= D in place, then a butterfly reduce-scatter
@@ -930,10 +1008,16 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     // counter and, once all nch have added, sums the partials in chunk
                     // order -- XP threads per entry, each over a fixed third (or so) of
                     // the chunks, the XP pieces added in piece order in LDS
-                    const size_t cstride = (size_t)nblk * SL;  // between one chunk's slabs and the next's
-                    const double* pb = sy.slabs + ((size_t)tk.slab0 * nblk + t) * SL;
-                    (void)CHK(((size_t)(tk.slab0 + nch - 1) * nblk + t) * SL + SL - 1, sy.lim_slab);  // the row's last slab
-                    if (xin) st_sc1(const_cast<double*>(pb) + tk.chunk * cstride + xe, (double)val);
+                    // addresses: the slab base plus 32-bit byte offsets (the task's xrow / xown /
+                    // xstr from the host, which keeps the slab area under 2^32 bytes)
+                    char* const sb = reinterpret_cast<char*>(a.slabs);
+                    // (opaque: offsets strength-reduced over the block loop would sit in VGPRs across it)
+                    uint32_t tb = t * (uint32_t)(SL * sizeof(double));
+                    asm volatile("" : "+s"(tb));
+                    const uint32_t xb = (uint32_t)xe * (uint32_t)sizeof(double);
+                    (void)CHK((size_t)xrow + (size_t)(nch - 1) * xstr + tb + SL * sizeof(double) - 1,
+                              cold_here(a.cold)->lim_slab * sizeof(double));  // the row's last slab
+                    if (xin) st_sc1(reinterpret_cast<double*>(sb + (xown + tb + xb)), (double)val);
                     asm volatile("" ::: "memory");
                     pf();
                     asm volatile("" ::: "memory");
@@ -944,7 +1028,7 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     else
                         wait_vmcnt<0>();
                     lds_barrier();
-                    uint32_t* cnt = sy.counters + CHK((size_t)tk.cnt0 + t, sy.ncounters);
+                    uint32_t* cnt = a.counters + CHK(cnt0 + t, a.ncounters);
                     if (threadIdx.x == 0) {
                         // no return value to wait for: the poll follows at once
                         __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -952,7 +1036,7 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                         while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nch) {
                             __builtin_amdgcn_s_sleep(1);
                             if (++spins > (1u << 26)) {  // give up: flag, never hang the device
-                                __hip_atomic_store(sy.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_store(a.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                 break;
                             }
                         }
@@ -960,17 +1044,21 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     lds_barrier();
                     if (xpart < XP) {
                         const uint32_t c0 = xpart * nch / XP, c1 = (xpart + 1) * nch / XP;
-                        const double* p0 = pb + xe;
+                        const uint32_t p0 = xrow + tb + xb;
+                        // chunk c + u: a scalar base per u and one lane offset for the 8 loads
+                        auto slab = [&](uint32_t c_, uint32_t u_) {
+                            return reinterpret_cast<const double*>(sb + (size_t)(u_ * xstr) + (p0 + c_ * xstr));
+                        };
                         double sum = 0.0;
                         uint32_t c = c0;
                         for (; c + 8 <= c1; c += 8) {  // 8 sc1 loads in flight
                             double v[8];
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) v[u] = ld_sc1(p0 + (c + u) * cstride);
+                            for (int u = 0; u < 8; ++u) v[u] = ld_sc1(slab(c, u));
 #pragma unroll
                             for (int u = 0; u < 8; ++u) sum += v[u];
                         }
-                        for (; c < c1; ++c) sum += ld_sc1(p0 + c * cstride);
+                        for (; c < c1; ++c) sum += ld_sc1(slab(c, 0));
                         xsum[xpart][xe] = sum;
                     }
                     lds_barrier();
@@ -995,8 +1083,12 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     // the block's old values, hyperparameters and normals (zero padded)
                     T sg, mu;
                     if constexpr (SMG) {
-                        sg = a.sig[kk];
-                        mu = a.mu[kk];
+                        // a scalar base per block and the lane's column: no per-lane 64-bit address
+                        // held across the block loop
+                        const T* sgp = a.sig + t * GB;
+                        asm volatile("" : "+s"(sgp));
+                        sg = sgp[ci];
+                        mu = sgp[Kp + ci];
                     } else {
                         sg = sgL[kk];
                         mu = muL[kk];
@@ -1011,7 +1103,9 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     dlt = gblock_solve_lds(&Rr[ci * GLD], Bq, A - old + Bq * (Cc + P * old));
                     if (lane < GB && wr == 0) {
                         if constexpr (DIRECT) {
-                            if (kin) a.own[(size_t)CHK(row, a.lim_rows) * Kp + kk] = old + dlt;
+                            T* orow = a.own + ((size_t)CHK(row_d, cold_here(a.cold)->lim_rows) * Kp + t * GB);
+                            asm volatile("" : "+s"(orow));
+                            if (kin) orow[ci] = old + dlt;
                         } else {
                             if (kin) newS[kk] = old + dlt;
                         }
@@ -1047,16 +1141,24 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
             // order (no per-vector branches)
             __syncthreads();
             double sq = 0.0, trs = 0.0;
-            for (uint32_t x = threadIdx.x; x < n; x += 64 * NW) {
-                const T e = eL[x];
-                a.E_other[CHK(pmL[x], a.lim_other)] = e;
-                sq += (double)(e * e);
-                if (a.row_tr) {
-                    const T r = a.r_this[beg + x];
-                    T pr = r - e;
-                    pr = (pr < a.hi) ? pr : a.hi;
-                    pr = (a.lo < pr) ? pr : a.lo;
-                    trs += (double)((pr - r) * (pr - r));
+            {  // ---- the cold block again, read here
+                const ColdP<T> ce = cold_here(a.cold);
+                const auto Eo = glob(ce->E_other);
+                const bool tr = ce->row_tr != nullptr;
+                const auto rt = glob(ce->r_this);
+                const T lo = ce->lo, hi = ce->hi;
+                const uint32_t beg = tr ? task_here().beg : 0u;
+                for (uint32_t x = threadIdx.x; x < n; x += 64 * NW) {
+                    const T e = eL[x];
+                    Eo[CHK(pmL[x], ce->lim_other)] = e;
+                    sq += (double)(e * e);
+                    if (tr) {
+                        const T r = rt[beg + x];
+                        T pr = r - e;
+                        pr = (pr < hi) ? pr : hi;
+                        pr = (lo < pr) ? pr : lo;
+                        trs += (double)((pr - r) * (pr - r));
+                    }
                 }
             }
             return GresSums{sq, trs};
@@ -1071,13 +1173,14 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
         else
             sums = body(std::integral_constant<int, VW>{});
         // ---- new own row: whole rows write it, split rows stage it (k_split_finish publishes)
-        if (!DIRECT && tk.chunk == 0)
-            for (uint32_t k = threadIdx.x; k < K; k += 64 * NW) {
-                if (nch > 1)
-                    static_cast<T*>(sy.newown)[(size_t)CHK(tk.slab0, sy.lim_chunk) * Kp + k] = newS[k];
-                else
-                    a.own[(size_t)CHK(row, a.lim_rows) * Kp + k] = newS[k];
-            }
+        const ColdP<T> cz = cold_here(a.cold);
+        const SplitTask tk = task_here();
+        const uint32_t row = tk.row;
+        if (!DIRECT && tk.chunk == 0) {
+            const auto dst = nch > 1 ? glob(cz->newown) + (size_t)CHK(tk.slab0, cz->lim_chunk) * Kp
+                                     : glob(cz->own) + (size_t)CHK(row, cz->lim_rows) * Kp;
+            for (uint32_t k = threadIdx.x; k < K; k += 64 * NW) dst[k] = newS[k];
+        }
         double dsq = wave_sum(sums.sq);
         double dtr = wave_sum(sums.tr);
         if (lane == 0) {
@@ -1093,11 +1196,11 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                 dtr += red2[w][1];
             }
             if (nch > 1) {
-                sy.chunk_sq[CHK(tk.slab0 + tk.chunk, sy.lim_chunk)] = dsq;
-                sy.chunk_tr[CHK(tk.slab0 + tk.chunk, sy.lim_chunk)] = dtr;
+                cz->chunk_sq[CHK(tk.slab0 + tk.chunk, cz->lim_chunk)] = dsq;
+                cz->chunk_tr[CHK(tk.slab0 + tk.chunk, cz->lim_chunk)] = dtr;
             } else {
-                if (a.row_sq) a.row_sq[row] = dsq;
-                if (a.row_tr) a.row_tr[row] = dtr;
+                if (cz->row_sq) cz->row_sq[row] = dsq;
+                if (cz->row_tr) cz->row_tr[row] = dtr;
             }
         }
         __syncthreads();  // LDS (ids, residuals, newS, red2) is reused by the next task
@@ -1106,14 +1209,13 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
 }
 template <typename T, int NW, int SIDE>
 __global__ __launch_bounds__(64 * NW, 4) void k_gres(
-    const SplitTask* __restrict__ tasks, uint32_t ntask, HalfArgs<T> a, SplitSync sy) {
-    gres_run<T, NW, SIDE, false>(tasks, nullptr, ntask, a, sy);
+    const SplitTask* __restrict__ tasks, uint32_t ntask, GresHot<T> a) {
+    gres_run<T, NW, SIDE, false>(tasks, nullptr, ntask, a);
 }
 template <typename T, int NW, int SIDE, int KL>
 __global__ __launch_bounds__(64 * NW, 4) void k_grow(
-    const uint32_t* __restrict__ rows, uint32_t nrows, HalfArgs<T> a) {
-    const SplitSync sy{};
-    gres_run<T, NW, SIDE, true, KL>(nullptr, rows, nrows, a, sy);
+    const uint32_t* __restrict__ rows, uint32_t nrows, GresHot<T> a) {
+    gres_run<T, NW, SIDE, true, KL>(nullptr, rows, nrows, a);
 }
 
 // Split rows: publish the new own rows and fold the chunk partial sums; and (every launch, with
@@ -1689,13 +1791,70 @@ hipError_t launch_gblock_nw(int nw, const uint32_t* rows, uint32_t nrows, const 
     return hipGetLastError();
 }
 
+template <typename T>
+GresCold<T> gres_cold(const HalfArgs<T>& a, const SplitSync* sy) {
+    GresCold<T> c{};
+    c.ptr = a.ptr;
+    c.part = a.part;
+    c.perm = a.perm;
+    c.E_this = a.E_this;
+    c.E_other = a.E_other;
+    c.r_this = a.r_this;
+    c.own = a.own;
+    c.zbuf = a.zbuf;
+    c.sig = a.sig;
+    c.row_sq = a.row_sq;
+    c.row_tr = a.row_tr;
+    c.lo = a.lo;
+    c.hi = a.hi;
+    c.zrow = a.zrow;
+    c.e_from_dot = a.e_from_dot;
+    c.lim_partner = a.lim_partner;
+    c.lim_other = a.lim_other;
+    c.lim_this = a.lim_this;
+    c.lim_rows = a.lim_rows;
+    if (sy) {
+        c.chunk_sq = sy->chunk_sq;
+        c.chunk_tr = sy->chunk_tr;
+        c.newown = static_cast<T*>(sy->newown);
+        c.prof = sy->prof;
+        c.lim_slab = sy->lim_slab;
+        c.lim_chunk = sy->lim_chunk;
+    }
+    return c;
+}
+// the by-value arguments of a launch whose cold block is d_cold
+template <typename T>
+static GresHot<T> gres_hot(const HalfArgs<T>& a, const SplitSync* sy, const GresCold<T>* d_cold) {
+    GresHot<T> h{};
+    h.partner = a.partner;
+    h.cold = d_cold;
+    if (!sy) {  // k_grow's: k_gres reads neither
+        h.own = a.own;
+        h.sig = a.sig;
+    }
+    h.tau = a.tau;
+    h.K = a.K;
+    h.Kp = a.Kp;
+    h.sd_is_var = a.sd_is_var;
+    if (sy) {
+        h.slabs = sy->slabs;
+        h.counters = sy->counters;
+        h.timeout = sy->timeout;
+        h.ncounters = sy->ncounters;
+    }
+    return h;
+}
+
 // Whole rows of a Gram-block bin on the streaming kernel's code, one workgroup per row:
 // one wave per row (nw = 1: rows of <= 128 f64 / 256 f32 ratings) or two (nw = 2: twice that)
 template <typename T>
-hipError_t launch_grow(int nw, const uint32_t* rows, uint32_t nrows, const HalfArgs<T>& a, hipStream_t st) {
+hipError_t launch_grow(int nw, const uint32_t* rows, uint32_t nrows, const HalfArgs<T>& ha, const GresCold<T>* d_cold,
+                       hipStream_t st) {
     if (nrows == 0) return hipSuccess;
-    if (a.K > 256) return hipErrorInvalidValue;
-    const bool side = a.tag == TAG_ITEMS;
+    if (ha.K > 256 || !d_cold || ha.mu != ha.sig + ha.Kp) return hipErrorInvalidValue;
+    const bool side = ha.tag == TAG_ITEMS;
+    const GresHot<T> a = gres_hot<T>(ha, nullptr, d_cold);
     // Kp <= 128: the row's sigma and mu in LDS too (KL = 128); larger K: from memory (KL = 256)
     auto go = [&](auto kl) {
         constexpr int KL = decltype(kl)::value;
@@ -1714,7 +1873,7 @@ hipError_t launch_grow(int nw, const uint32_t* rows, uint32_t nrows, const HalfA
         }
         return hipGetLastError();
     };
-    return a.Kp <= 128 && !(a.tune & 0x1000u) ? go(std::integral_constant<int, 128>{})
+    return ha.Kp <= 128 && !(ha.tune & 0x1000u) ? go(std::integral_constant<int, 128>{})
                                                : go(std::integral_constant<int, 256>{});
 }
 uint32_t grow_maxdeg(int nw, bool f64) { return 4u * (uint32_t)nw * (f64 ? GresW<double>::VW : GresW<float>::VW); }
@@ -1742,9 +1901,9 @@ int gstream_blocks_per_cu(uint32_t cmax, uint32_t tune) {
 
 template <typename T>
 hipError_t launch_gstream(const SplitTask* tasks, uint32_t ntask, uint32_t grid, const SplitRow* srows, uint32_t nsrow,
-                          const HalfArgs<T>& a, const SplitSync& sy, hipStream_t st) {
+                          const HalfArgs<T>& a, const SplitSync& sy, const GresCold<T>* d_cold, hipStream_t st) {
     if (ntask == 0) return hipSuccess;
-    if (a.K > 256 || sy.cmax == 0 || grid == 0) return hipErrorInvalidValue;
+    if (a.K > 256 || sy.cmax == 0 || grid == 0 || !d_cold || a.mu != a.sig + a.Kp) return hipErrorInvalidValue;
     hipError_t err;
     // Tasks are claimed from a queue in list order by running workgroups, so only
     // the most recently claimed split row can have chunks still unclaimed, and its
@@ -1754,9 +1913,8 @@ hipError_t launch_gstream(const SplitTask* tasks, uint32_t ntask, uint32_t grid,
     // which checks that the whole grid fits (the host sizes it to residency); a
     // process that did so faulted in exit() under rocprofv3 (r04s16).
     const SplitTask* tp = tasks;
-    HalfArgs<T> ap = a;
-    SplitSync syp = sy;
-    void* args[] = {(void*)&tp, (void*)&ntask, (void*)&ap, (void*)&syp};
+    GresHot<T> hp = gres_hot<T>(a, &sy, d_cold);
+    void* args[] = {(void*)&tp, (void*)&ntask, (void*)&hp};
     const void* fn = gstream_fn<T>(a.tune, a.tag == TAG_ITEMS ? 1u : 0u);
     const dim3 g(std::min(grid, ntask)), b(64 * gres_nw(a.tune));
     if (a.tune & 0x1000000u)
@@ -1910,9 +2068,11 @@ hipError_t launch_unpack(const T* recv, const uint32_t* idx, uint64_t n, T* E, h
     template hipError_t launch_gblock<T>(int, const uint32_t*, uint32_t, const HalfArgs<T>&, hipStream_t);          \
     template hipError_t launch_gblock_nw<T>(int, const uint32_t*, uint32_t, const HalfArgs<T>&, hipStream_t);       \
     template hipError_t launch_gstream<T>(const SplitTask*, uint32_t, uint32_t, const SplitRow*, uint32_t,           \
-                                          const HalfArgs<T>&, const SplitSync&, hipStream_t);                        \
+                                          const HalfArgs<T>&, const SplitSync&, const GresCold<T>*, hipStream_t);    \
+    template GresCold<T> gres_cold<T>(const HalfArgs<T>&, const SplitSync*);                                        \
     template int gstream_blocks_per_cu<T>(uint32_t, uint32_t);                                                      \
-    template hipError_t launch_grow<T>(int, const uint32_t*, uint32_t, const HalfArgs<T>&, hipStream_t);            \
+    template hipError_t launch_grow<T>(int, const uint32_t*, uint32_t, const HalfArgs<T>&, const GresCold<T>*,      \
+                                       hipStream_t);                                                                \
     template uint32_t gstream_cmax<T>(uint32_t);                                                                    \
     template hipError_t launch_resid<T>(const ResidTask*, uint32_t, const uint32_t*, uint32_t, uint32_t,              \
                                         const uint32_t*, const uint32_t*, const T*, const T*, const T*, uint32_t,     \

@@ -29,7 +29,7 @@ __device__ __noinline__ uint64_t chk_fail(uint64_t i, uint64_t lim, int line) {
 
 #ifdef SBMF_KPROF_BUILD
 // KPROF=1 (run with SBMF_KPROF=1): wave 0's clock cycles per phase, added into
-// a.prof / sy.prof (sbmf.cpp prints them).  k_gblock: multi-wave rows only.
+// a.prof / the streaming kernels' cold block's prof (sbmf.cpp prints them).  k_gblock: multi-wave rows only.
 // k_gres: also per chunk-count class (whole rows / 2..16 chunks / more) at
 // [32 + 24*SIDE + 8*cls], slot 7 of a class counting its tasks.
 #define SBMF_GBLOCK_PHASES(on)                                                   \
@@ -41,20 +41,20 @@ __device__ __noinline__ uint64_t chk_fail(uint64_t i, uint64_t lim, int line) {
             tp_ = now;                                                           \
         }                                                                        \
     }
-#define SBMF_GRES_PHASES(nch)                                                                          \
-    unsigned long long tp_ = (sy.prof && threadIdx.x == 0) ? clock64() : 0ull;                         \
+#define SBMF_GRES_PHASES(nch, prof_)                                                                        \
+    unsigned long long tp_ = ((prof_) && threadIdx.x == 0) ? clock64() : 0ull;                         \
     unsigned long long* const pcls_ =                                                                  \
-        sy.prof ? sy.prof - 8 * SIDE + 32 + 24 * SIDE + 8 * ((nch) == 1 ? 0 : (nch) <= 16 ? 1 : 2) : nullptr; \
-    if (sy.prof && threadIdx.x == 0) atomicAdd(&pcls_[7], 1ull);                                       \
+        (prof_) ? (prof_) - 8 * SIDE + 32 + 24 * SIDE + 8 * ((nch) == 1 ? 0 : (nch) <= 16 ? 1 : 2) : nullptr; \
+    if ((prof_) && threadIdx.x == 0) atomicAdd(&pcls_[7], 1ull);                                       \
     auto stamp = [&](int ph) {                                                                         \
-        if (sy.prof && threadIdx.x == 0) {                                                             \
+        if ((prof_) && threadIdx.x == 0) {                                                             \
             const unsigned long long now = clock64();                                                  \
-            atomicAdd(&sy.prof[ph], now - tp_);                                                        \
+            atomicAdd(&(prof_)[ph], now - tp_);                                                        \
             atomicAdd(&pcls_[ph], now - tp_);                                                          \
             tp_ = now;                                                                                 \
         }                                                                                              \
     }
 #else
 #define SBMF_GBLOCK_PHASES(on) auto stamp = [](int) {}
-#define SBMF_GRES_PHASES(nch) auto stamp = [](int) {}
+#define SBMF_GRES_PHASES(nch, prof_) auto stamp = [](int) {}
 #endif

@@ -331,6 +331,13 @@ struct sbmf_ctx {
     DBuf d_kprof;
     DBuf d_rtasks, d_rtptr, d_rtsq;  // residual recompute (item side)
     DBuf d_xslabs, d_xcnt, d_xchunk_sq, d_xchunk_tr, d_xnewown;
+    // The streaming row kernels' cold argument blocks (GresCold, kernels.h), one slot of
+    // kColdSlot bytes per (stage, side, launch shape: stream set 0, set 1, k_grow), with the host's
+    // copy of what the device holds: a block is uploaded when it differs from that copy (the
+    // first half-sweep after set_data or a configuration change), never per half otherwise.
+    static constexpr size_t kColdSlot = 256;
+    DBuf d_gcold;
+    std::vector<unsigned char> h_gcold;
     bool time_kinds = true;   // this sweep records every launch kind's events (else the streaming kind's only)
     size_t xset_nx = 1, xset_nr = 1;  // set 0's split chunks / rows: set 1's areas follow them
     DBuf d_tu, d_ti, d_tr, d_tsum, d_tpart;
@@ -604,7 +611,12 @@ static void prepare_T(sbmf_ctx* c) {
     c->xset_nr = std::max<size_t>(nrk[0], 1);
     {
         const size_t nx = c->xset_nx + std::max<size_t>(nxk[1], 1), nr = c->xset_nr + std::max<size_t>(nrk[1], 1);
-        c->d_xslabs.alloc(nx * nblk * (16 * 16 + 16) * sizeof(double));
+        // the streaming kernel addresses a set's slabs with 32-bit byte offsets (SplitTask::xrow ...)
+        if ((uint64_t)nx * nblk * SLAB_DOUBLES * sizeof(double) >= 0xffffffffull)
+            fail(SBMF_E_ARG, "split-row exchange area of %zu chunks at K=%u exceeds 2^32 bytes", nx, c->K);
+        c->d_xslabs.alloc(nx * nblk * SLAB_DOUBLES * sizeof(double));
+        c->d_gcold.alloc((size_t)c->nstages * 6 * sbmf_ctx::kColdSlot);
+        c->h_gcold.assign((size_t)c->nstages * 6 * sbmf_ctx::kColdSlot, 0xff);  // nothing uploaded yet
         // + each set's task-queue head.  Zeroed once here: every streaming launch leaves its set's
         // area zero again (k_split_finish clears it after k_gres)
         c->d_xcnt.alloc((nr * nblk + 2 + 3) / 4 * 4 * sizeof(uint32_t));
@@ -778,14 +790,19 @@ static void build_stream_tasks(const Side& s, Side::StreamSet& S, const std::vec
         if (nch > gres)
             fail(SBMF_E_ARG, "row %u has %u ratings: more than %u co-resident chunks of %u", r, n, gres, cmax);
         if (nch == 1) {
-            S.stasks.push_back(SplitTask{r, s.ptr[r], n, 1, 0, 0, 0, 0});
+            S.stasks.push_back(SplitTask{r, s.ptr[r], n, 1, 0, 0, 0, 0, 0, 0, {0, 0}});
         } else {
             const uint32_t slab0 = S.nxchunk;
             const uint32_t cnt0 = (uint32_t)S.xrows.size() * nblk;
             const uint32_t per = (n + nch - 1) / nch;
+            // byte offsets of the row's slabs in the set's area (set_data checks the area < 2^32 bytes)
+            const uint64_t xstr = (uint64_t)nblk * SLAB_DOUBLES * sizeof(double), xrow = (uint64_t)slab0 * xstr;
+            if (xrow + (uint64_t)nch * xstr >= 0xffffffffull)
+                fail(SBMF_E_ARG, "split-row exchange area exceeds 2^32 bytes at row %u", r);
             for (uint32_t c = 0; c < nch; ++c) {
                 const uint32_t b = c * per, e = std::min(n, b + per);
-                S.stasks.push_back(SplitTask{r, s.ptr[r] + b, e - b, nch, c, slab0, cnt0, 0});
+                S.stasks.push_back(SplitTask{r, s.ptr[r] + b, e - b, nch, c, slab0, cnt0, (uint32_t)xrow,
+                                             (uint32_t)(xrow + c * xstr), (uint32_t)xstr, {0, 0}});
             }
             S.xrows.push_back(SplitRow{r, slab0, nch, 0});
             S.nxchunk += nch;
@@ -990,6 +1007,27 @@ static HalfArgs<T> half_args(sbmf_ctx* c, bool users) {
     return a;
 }
 
+// The device copy of a streaming launch's cold block, in slot `slot` ((stage * 2 + side) * 3 +
+// shape) of d_gcold: uploaded here if it differs from what the device holds.  The block's fields
+// are the context's buffers and configuration, fixed from set_data on, and every stage has slots
+// of its own, so in a chain of sweeps each slot is uploaded the first time its launch runs and
+// never again, with one stage per half or several; a change (new buffers, another tune) drains
+// the streams that may still read the old block first.  SBMF_COLD_LOG=1 reports each upload.
+template <typename T>
+static const GresCold<T>* cold_block(sbmf_ctx* c, int slot, const GresCold<T>& cold) {
+    static_assert(sizeof(GresCold<T>) <= sbmf_ctx::kColdSlot, "cold block slot");
+    unsigned char* h = c->h_gcold.data() + (size_t)slot * sbmf_ctx::kColdSlot;
+    unsigned char* d = c->d_gcold.as<unsigned char>() + (size_t)slot * sbmf_ctx::kColdSlot;
+    if (std::memcmp(h, &cold, sizeof(cold)) != 0) {
+        for (hipStream_t s : {c->st, c->sto, c->sto2}) HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(d, &cold, sizeof(cold), hipMemcpyHostToDevice));
+        std::memcpy(h, &cold, sizeof(cold));
+        static const bool log = std::getenv("SBMF_COLD_LOG") != nullptr;
+        if (log) std::fprintf(stderr, "[sbmf] cold block upload: slot %d, sweep %u\n", slot, c->sweep);
+    }
+    return reinterpret_cast<const GresCold<T>*>(d);
+}
+
 // `start` (optional): a timing event the caller has just recorded on the compute stream with
 // nothing queued there since.  The half then forks its side streams from it and, when nothing
 // precedes its first kind on the compute stream, times that kind from it: two event records
@@ -1093,7 +1131,8 @@ static void run_half(sbmf_ctx* c, bool users, uint32_t stage, hipEvent_t start =
                        : k == GK_W16 && !(tn & 0x400u) && !(tn & 8u)  ? 1
                                                                       : 0;
         if (gw) {
-            HIPCHK(launch_grow<T>(gw, g.d_bins[k].as<uint32_t>(), (uint32_t)g.bin_rows[k].size(), a, st));
+            HIPCHK(launch_grow<T>(gw, g.d_bins[k].as<uint32_t>(), (uint32_t)g.bin_rows[k].size(), a,
+                                  cold_block<T>(c, (2 * (int)stage + sd) * 3 + 2, gres_cold<T>(a, nullptr)), st));
         } else if (k < GK_NUM && k >= GK_B2 && !(c->cfg.tune & 4u)) {
             for (const auto& gs : g.gsub[k])
                 HIPCHK(launch_gblock_nw<T>((int)gs[0], g.d_bins[k].as<uint32_t>() + gs[1], gs[2], a, st));
@@ -1108,7 +1147,7 @@ static void run_half(sbmf_ctx* c, bool users, uint32_t stage, hipEvent_t start =
                 const size_t ox = set ? c->xset_nx : 0, orow = set ? c->xset_nr : 0;
                 SplitSync sy{};
                 sy.nblk = (c->K + 15) / 16;
-                sy.slabs = c->d_xslabs.as<double>() + ox * sy.nblk * (16 * 16 + 16);
+                sy.slabs = c->d_xslabs.as<double>() + ox * sy.nblk * SLAB_DOUBLES;
                 sy.counters = c->d_xcnt.as<uint32_t>() + (set ? orow * sy.nblk + 1 : 0);
                 sy.ncounters = (uint32_t)S.xrows.size() * sy.nblk;
                 sy.chunk_sq = c->d_xchunk_sq.as<double>() + ox;
@@ -1116,13 +1155,14 @@ static void run_half(sbmf_ctx* c, bool users, uint32_t stage, hipEvent_t start =
                 sy.newown = c->d_xnewown.as<T>() + ox * c->Kp;
                 sy.timeout = reinterpret_cast<uint32_t*>(c->d_res.as<double>() + RES_TIMEOUT);
                 sy.cmax = S.cmax;
-                sy.lim_slab = (uint64_t)(c->d_xslabs.bytes / sizeof(double)) - ox * sy.nblk * (16 * 16 + 16);
+                sy.lim_slab = (uint64_t)(c->d_xslabs.bytes / sizeof(double)) - ox * sy.nblk * SLAB_DOUBLES;
                 sy.lim_chunk = (uint32_t)(c->d_xchunk_sq.bytes / sizeof(double) - ox);
                 sy.prof = c->kprof && set == c->kprof_set ? c->d_kprof.as<unsigned long long>() + 8 * (users ? 0 : 1) : nullptr;
                 HalfArgs<T> as = a;
                 as.tune = S.tune;
                 HIPCHK(launch_gstream<T>(g.d_stasks[set].as<SplitTask>(), (uint32_t)S.stasks.size(), S.sgrid,
-                                         g.d_xrows[set].as<SplitRow>(), (uint32_t)S.xrows.size(), as, sy, ss));
+                                         g.d_xrows[set].as<SplitRow>(), (uint32_t)S.xrows.size(), as, sy,
+                                         cold_block<T>(c, (2 * (int)stage + sd) * 3 + set, gres_cold<T>(as, &sy)), ss));
                 if (ss == c->st) st_busy = true;
             }
             if (sov) {  // the streaming stage ends with both sets
