@@ -76,22 +76,22 @@ struct SplitTask {
     uint32_t nch;    // chunks of the row (1 = whole row, no exchange)
     uint32_t chunk;  // chunk index within the row
     uint32_t slab0;  // split rows: first chunk slab of the row (also its new-own slot)
-    uint32_t cnt0;   // split rows: first block counter of the row
     // split rows, byte offsets in the set's slab area (the host checks the area is < 2^32 bytes),
     // so the exchange addresses are the slab base plus 32-bit offsets:
     uint32_t xrow;   // block 0 of the row's first chunk
     uint32_t xown;   // block 0 of this chunk: xrow + chunk * xstr
     uint32_t xstr;   // from one chunk's slabs to the next's: nblk * SLAB_DOUBLES * 8
-    uint32_t pad[2];
+    uint32_t pad[3];
 };
 constexpr uint32_t SLAB_DOUBLES = 16 * 16 + 16;  // per (chunk, block): 16x16 image | c
 struct SplitRow {
     uint32_t row, slab0, nch, pad;
 };
 struct SplitSync {
-    double* slabs;       // [nchunk_total][nblk][16*16+16]
-    uint32_t* counters;  // [nsplit_rows * nblk], then the task-queue head: zero at launch (k_split_finish clears them)
-    uint32_t ncounters;
+    // [nchunk_total][nblk][16*16+16]; at launch every word of the area is the sentinel, all ones
+    // (set_data fills it, the chunks and k_split_finish put it back: kernels.hip, XSENT)
+    double* slabs;
+    uint32_t* qhead;     // the set's task-queue head: zero at launch (k_split_finish clears it)
     uint32_t nblk;       // ceil(K/16)
     double* chunk_sq;    // [nchunk_total]
     double* chunk_tr;    // [nchunk_total]
@@ -124,6 +124,7 @@ struct GresCold {
     double* chunk_sq;    // split rows (k_gres)
     double* chunk_tr;
     T* newown;
+    uint32_t* timeout;   // set to 1 when a split row's hand-off gives up (read on that path only)
     T lo, hi;
     uint32_t zrow;
     int e_from_dot;
@@ -150,9 +151,9 @@ int gstream_blocks_per_cu(uint32_t cmax, uint32_t tune);
 // (<= residency) workgroups.  Tasks are one list, claimed in order from a queue
 // head by whichever workgroup is free; a split row's chunks are consecutive, so
 // a chunk only waits for peers that the next free workgroups claim.  Split rows
-// are then published by k_split_finish.  sy.counters[0..ncounters] must be zero
-// when the launch starts: sbmf.cpp clears every set's counters with one memset
-// per half, ahead of the half's launches.  d_cold: gres_cold(a, &sy) in device memory, valid
+// are then published by k_split_finish.  *sy.qhead must be zero and the set's slab
+// area all sentinel words when the launch starts: sbmf.cpp sets both once in
+// set_data, and every launch leaves them so.  d_cold: gres_cold(a, &sy) in device memory, valid
 // until the launch has run.
 template <typename T>
 hipError_t launch_gstream(const SplitTask* tasks, uint32_t ntask, uint32_t grid, const SplitRow* srows, uint32_t nsrow,

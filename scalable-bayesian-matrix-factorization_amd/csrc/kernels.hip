@@ -37,10 +37,15 @@
 //   CHK(i, extent)           a global index (CHECK=1: validated, printed, redirected)
 //   SBMF_GBLOCK_PHASES(on)   declares stamp(phase) in k_gblock (KPROF=1: wave 0's
 //   SBMF_GRES_PHASES(nch, p) cycles per phase) / in k_gres' task loop
+//                            (and stamp_first(phase): once per block, after stamp(7))
+//   SBMF_XSENT_CHECK(bad)    CHECK=1: a split row's partial with the slab sentinel's bits
 #ifndef SBMF_KERNELS_INSTR_H_
 #define CHK(i, lim) (i)
 #define SBMF_GBLOCK_PHASES(on) auto stamp = [](int) {}
-#define SBMF_GRES_PHASES(nch, prof_) auto stamp = [](int) {}
+#define SBMF_GRES_PHASES(nch, prof_) \
+    auto stamp = [](int) {};         \
+    auto stamp_first = [](int) {}
+#define SBMF_XSENT_CHECK(bad) ((void)0)
 #endif
 
 namespace sbmf {
@@ -612,21 +617,55 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : RPW), GBLOCK_OCC(T, V)) void k_
 // Per block t, per vector: apply D_{t-1} with the held slice, then issue the
 // gather of slice t into the same registers; then accumulate block t.  The
 // task's partner ids, residuals, scatter targets and ratings sit in LDS.
-// Split rows hand their (G_B, c_B) partials over without fences: each chunk
-// writes its packed partial (152 doubles: the lower triangle of G_B with its
-// diagonal, then c_B) with write-through (sc1) stores, drains them and adds
-// once to the block's agent-scope counter; every chunk polls the counter (sc1
-// loads) for nch and then reads all partials -- MI355X_MICROARCH.md hand-off
-// table, first row.  The chunk sum of an entry is split over the workgroup's
+// Split rows hand their (G_B, c_B) partials over without fences, flags or
+// counters: each chunk writes its packed partial (152 doubles: the lower
+// triangle of G_B with its diagonal, then c_B) with write-through (sc1) stores
+// and does not wait for them; every chunk reads all partials with 8-byte sc1
+// loads and takes a word as soon as it no longer holds the slab sentinel
+// (XSENT below; an aligned 8-byte word is never seen torn), reloading a batch
+// that still has one.  A chunk puts the sentinel back over its slab of block
+// t-1 once it has read block t of every chunk, k_split_finish over the last
+// block's.  The chunk sum of an entry is split over the workgroup's
 // spare threads (3 per entry for 8 waves), each summing a fixed range of
 // chunks in order, the pieces added in piece order, so it never depends on
 // which chunk arrives last and every chunk gets the same bits.
 __device__ __forceinline__ void st_sc1(double* p, double v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ double ld_sc1(const double* p) {
+__device__ __forceinline__ void st_sc1(uint64_t* p, uint64_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint64_t ld_sc1(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The sentinel of the slab area: a word no chunk has published yet (since the area was filled,
+// or since its owner or k_split_finish put it back) holds all ones, and a reader takes a word
+// for a partial as soon as it holds anything else -- the partial is its own flag, with no
+// counter, no drained store and no poll beside it.  A partial never has these bits: all ones
+// is a negative quiet NaN with every payload bit set, and the arithmetic that makes a partial
+// (MFMA, multiply, add, float -> double) yields a finite value, an infinity, the canonical
+// quiet NaN (0x7ff8000000000000), or a quieted copy of a NaN operand -- so it yields all ones
+// only from an all-ones operand, and there is none: the ratings and initial factors come from
+// the host as finite numbers, every later value is such a result, and a slab word that equals
+// the sentinel is never converted to an operand (a reader retries instead, and after a timeout
+// the sweep is reported invalid).  An f32 partial widened to double has 29 zero payload bits.
+// CHECK=1 builds report a partial with these bits.
+constexpr uint64_t XSENT = ~0ull;
+// the sentinel made where it is stored (the compiler would keep the pair in VGPRs across the block loop)
+__device__ __forceinline__ uint64_t xsent_here() {
+    uint32_t w = ~0u;
+    asm volatile("" : "+v"(w));
+    return ((uint64_t)w << 32) | w;
+}
+__device__ __forceinline__ uint64_t xword(double v) { return (uint64_t)__double_as_longlong(v); }
+__device__ __forceinline__ double xdbl(uint64_t w) { return __longlong_as_double((long long)w); }
+// tuning: s_sleep units (64 clocks) between the publish and the first read, and before a reload
+#ifndef SBMF_XDELAY
+#define SBMF_XDELAY 0
+#endif
+#ifndef SBMF_XBACKOFF
+#define SBMF_XBACKOFF 1
+#endif
 struct GresSums {
     double sq, tr;
 };
@@ -677,11 +716,9 @@ struct GresHot {
     T* own;                 // k_grow (DIRECT) only: the solving wave writes the row itself
     const T* sig;           // k_grow at KL = 256 (SMG) only: [sig | mu] read per block
     double* slabs;          // k_gres: the set's slab area
-    uint32_t* counters;     // k_gres: block counters, then the queue head at [ncounters]
-    uint32_t* timeout;
+    uint32_t* qhead;        // k_gres: the set's task-queue head
     T tau;
     uint32_t K, Kp;
-    uint32_t ncounters;
     int sd_is_var;
 };
 // The cold block as constant memory behind a compiler barrier: loads through the returned pointer
@@ -796,7 +833,7 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
             if (it > 0 || ti >= ntask) break;
         } else {
             if (threadIdx.x == 0)
-                qti = __hip_atomic_fetch_add(a.counters + a.ncounters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                qti = __hip_atomic_fetch_add(a.qhead, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             ti = __builtin_amdgcn_readfirstlane(qti);  // uniform: the task record by scalar loads
             __syncthreads();  // every thread has its ticket before thread 0 claims the next
@@ -813,15 +850,15 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                 const uint32_t r = *lr;
                 const auto rp = glob(cold_here(a.cold)->ptr);
                 const uint32_t b = rp[r];
-                return SplitTask{r, b, rp[r + 1] - b, 1u, 0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+                return SplitTask{r, b, rp[r + 1] - b, 1u, 0u, 0u, 0u, 0u, 0u, {0u, 0u, 0u}};
             } else {
                 auto tq = (const __attribute__((address_space(4))) SplitTask*)(uintptr_t)(tasks + ti);
                 asm volatile("" : "+s"(tq));
                 return SplitTask{tq->row,  tq->beg,  tq->len,  tq->nch,  tq->chunk, tq->slab0,
-                                 tq->cnt0, tq->xrow, tq->xown, tq->xstr, {0u, 0u}};
+                                 tq->xrow, tq->xown, tq->xstr, {0u, 0u, 0u}};
             }
         };
-        uint32_t n, nch, xrow = 0, xown = 0, xstr = 0, cnt0 = 0;
+        uint32_t n, nch, xrow = 0, xown = 0, xstr = 0;
         {
             const SplitTask tk = task_here();
             n = tk.len;
@@ -830,7 +867,6 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                 xrow = tk.xrow;
                 xown = tk.xown;
                 xstr = tk.xstr;
-                cnt0 = tk.cnt0;
             }
         }
         if (n == 0) continue;  // empty round slot (uniform)
@@ -949,10 +985,9 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
             // pf: a prefetch of the next block's slices (NPF vector-memory loads per wave),
             // issued here so that it stays in flight through the block's exchange and draws.
             // Every barrier below is an LDS-only barrier (lds_barrier: __syncthreads() would
-            // wait vmcnt(0) and drain the prefetch); a split row's partial stores are issued
-            // before the prefetch and waited for with vmcnt(NPF).
-            auto finish_block = [&](const acc_t& g, T cc, uint32_t t, auto&& pf, auto npf) -> T {
-                constexpr int NPF = decltype(npf)::value;
+            // wait vmcnt(0) and drain the prefetch, and a split row's partial stores with it:
+            // nothing waits for those).
+            auto finish_block = [&](const acc_t& g, T cc, uint32_t t, auto&& pf, auto) -> T {
                 T Dl;
                 if (nch == 1) pf();
                 if constexpr (ONE) {
@@ -1004,10 +1039,10 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                 const bool xchg = nch > 1;
                 if (xchg) {
                     // cross-chunk sum over the row's chunks (see the header comment):
-                    // every chunk stores its packed partial, adds once to the block's
-                    // counter and, once all nch have added, sums the partials in chunk
-                    // order -- XP threads per entry, each over a fixed third (or so) of
-                    // the chunks, the XP pieces added in piece order in LDS
+                    // every chunk stores its packed partial and sums all nch partials in
+                    // chunk order, each word as soon as it is there -- XP threads per
+                    // entry, each over a fixed third (or so) of the chunks, the XP pieces
+                    // added in piece order in LDS
                     // addresses: the slab base plus 32-bit byte offsets (the task's xrow / xown /
                     // xstr from the host, which keeps the slab area under 2^32 bytes)
                     char* const sb = reinterpret_cast<char*>(a.slabs);
@@ -1017,51 +1052,81 @@ __device__ __forceinline__ void gres_run(const SplitTask* __restrict__ tasks, co
                     const uint32_t xb = (uint32_t)xe * (uint32_t)sizeof(double);
                     (void)CHK((size_t)xrow + (size_t)(nch - 1) * xstr + tb + SL * sizeof(double) - 1,
                               cold_here(a.cold)->lim_slab * sizeof(double));  // the row's last slab
+                    // publish: no wait for the store and no flag -- the word is its own flag
+                    SBMF_XSENT_CHECK(xin && xword((double)val) == XSENT);
                     if (xin) st_sc1(reinterpret_cast<double*>(sb + (xown + tb + xb)), (double)val);
                     asm volatile("" ::: "memory");
                     pf();
                     asm volatile("" ::: "memory");
-                    // this wave's partial stores (older than the prefetch) are done; the last block
-                    // prefetches nothing, so it waits for everything
-                    if (NPF > 0 && t + 1 < nblk)
-                        wait_vmcnt<NPF>();
-                    else
-                        wait_vmcnt<0>();
-                    lds_barrier();
-                    uint32_t* cnt = a.counters + CHK(cnt0 + t, a.ncounters);
-                    if (threadIdx.x == 0) {
-                        // no return value to wait for: the poll follows at once
-                        __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        uint32_t spins = 0;
-                        while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nch) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if (++spins > (1u << 26)) {  // give up: flag, never hang the device
-                                __hip_atomic_store(a.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                break;
-                            }
-                        }
-                    }
+                    stamp(7);  // cross-wave sum + publish
+                    if (SBMF_XDELAY > 0) __builtin_amdgcn_s_sleep(SBMF_XDELAY);
                     lds_barrier();
                     if (xpart < XP) {
                         const uint32_t c0 = xpart * nch / XP, c1 = (xpart + 1) * nch / XP;
                         const uint32_t p0 = xrow + tb + xb;
                         // chunk c + u: a scalar base per u and one lane offset for the 8 loads
+                        // (the lane offset is made opaque at every use: hoisted out of the
+                        // loop, the 8 addresses of a batch would sit in 16 VGPRs)
                         auto slab = [&](uint32_t c_, uint32_t u_) {
-                            return reinterpret_cast<const double*>(sb + (size_t)(u_ * xstr) + (p0 + c_ * xstr));
+                            uint32_t pc = p0 + c_ * xstr;
+                            asm volatile("" : "+v"(pc));
+                            return reinterpret_cast<const uint64_t*>(sb + (size_t)(u_ * xstr) + pc);
+                        };
+                        // A batch is valid when none of its words is the sentinel: (lo & hi) is all
+                        // ones for the sentinel only, so one unsigned maximum over the batch (m) and
+                        // one compare decide it.  miss(m): some lane of the wave has to read its
+                        // batch again -- the whole wave then does, after a short sleep, by going
+                        // round its loop without advancing (no loop nested in the read loops, no
+                        // lane mask held for one).  The reloads are counted: after seconds of them
+                        // the lanes set the timeout flag and take what they have -- a chunk whose
+                        // peers never come does not hang the device.  (The count in a VGPR and this
+                        // plain test: a scalar count, or a look at the flag to give up with the
+                        // first wave that does, costs the 4-wave kernel 2 more spilled SGPRs.)
+                        uint32_t spins = 0;
+                        auto miss = [&](uint32_t m) -> bool {
+                            if (!__builtin_amdgcn_ballot_w64(m == 0xffffffffu)) return false;
+                            if (++spins > (1u << 22)) {
+                                uint32_t one = 1u;  // (made here: not a register held across the loop)
+                                asm volatile("" : "+v"(one));
+                                __hip_atomic_store(glob(cold_here(a.cold)->timeout), one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                spins = 1u << 22;  // (no further wait in this block)
+                                return false;
+                            }
+                            __builtin_amdgcn_s_sleep(SBMF_XBACKOFF);
+                            return true;
                         };
                         double sum = 0.0;
                         uint32_t c = c0;
-                        for (; c + 8 <= c1; c += 8) {  // 8 sc1 loads in flight
-                            double v[8];
+                        while (c + 8 <= c1) {  // 8 sc1 loads in flight
+                            uint64_t v[8];
+                            uint32_t m = 0u;
 #pragma unroll
                             for (int u = 0; u < 8; ++u) v[u] = ld_sc1(slab(c, u));
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) sum += v[u];
+                            for (int u = 0; u < 8; ++u) m = max(m, (uint32_t)v[u] & (uint32_t)(v[u] >> 32));
+                            if (miss(m)) continue;
+                            stamp_first(8);  // publish to the first valid batch
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) sum += xdbl(v[u]);
+                            c += 8;
                         }
-                        for (; c < c1; ++c) sum += ld_sc1(slab(c, 0));
+                        while (c < c1) {
+                            const uint64_t v = ld_sc1(slab(c, 0));
+                            if (miss((uint32_t)v & (uint32_t)(v >> 32))) continue;
+                            stamp_first(8);
+                            sum += xdbl(v);
+                            ++c;
+                        }
                         xsum[xpart][xe] = sum;
                     }
                     lds_barrier();
+                    // Every thread of this chunk has now seen block t of every chunk of the row, and
+                    // a chunk publishes block t only after its loads of block t-1 have returned (its
+                    // block t depends on them through D_{t-1}): nobody reads this chunk's slab of
+                    // block t-1 again, and the thread that published an entry puts the sentinel
+                    // back.  (The last block's slab: k_split_finish.)
+                    if (xin && t > 0)
+                        st_sc1(reinterpret_cast<uint64_t*>(sb + (xown + tb + xb) - (uint32_t)(SL * sizeof(double))), xsent_here());
                     if (xin) {
                         double sum = xsum[0][xe];
 #pragma unroll
@@ -1219,7 +1284,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_grow(
 }
 
 // Split rows: publish the new own rows and fold the chunk partial sums; and (every launch, with
-// at least one block) put the set's split-row counters and queue head back to zero for the next
+// at least one block) put the set's queue head back to zero and the split rows' slabs of the last
+// k-block back to the sentinel (the chunks reset the earlier blocks' themselves) for the next
 // streaming launch on this area, in stream order after k_gres.  (That clear was a fill launch per
 // streaming stage on the compute stream: a kernel and a packet gap, r06s10 trace.  Done by
 // k_gres's last workgroup instead, the exit count kept sy alive across the task loop: spilled
@@ -1228,10 +1294,17 @@ __global__ __launch_bounds__(64 * NW, 4) void k_grow(
 template <typename T>
 __global__ __launch_bounds__(64) void k_split_finish(const SplitRow* __restrict__ srows, uint32_t nrows, HalfArgs<T> a,
                                                      SplitSync sy) {
-    for (uint32_t i = blockIdx.x * 64 + threadIdx.x; i <= sy.ncounters; i += gridDim.x * 64) sy.counters[i] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *sy.qhead = 0u;
     if (blockIdx.x >= nrows) return;
     const SplitRow sr = srows[blockIdx.x];
     const uint32_t K = a.K, Kp = a.Kp;
+    {  // the row's slabs of the last block: the packed entries of every chunk back to the sentinel
+        constexpr uint32_t SLP = GB * (GB + 1) / 2 + GB;
+        uint64_t* const last = reinterpret_cast<uint64_t*>(sy.slabs) + ((size_t)sr.slab0 * sy.nblk + (sy.nblk - 1)) * SLAB_DOUBLES;
+        for (uint32_t i = threadIdx.x; i < sr.nch * SLP; i += 64)
+            last[CHK((size_t)(i / SLP) * sy.nblk * SLAB_DOUBLES + i % SLP,
+                     sy.lim_slab - ((size_t)sr.slab0 * sy.nblk + (sy.nblk - 1)) * SLAB_DOUBLES)] = XSENT;
+    }
     for (uint32_t k = threadIdx.x; k < K; k += 64) a.own[(size_t)sr.row * Kp + k] = static_cast<const T*>(sy.newown)[(size_t)sr.slab0 * Kp + k];
     if (threadIdx.x == 0) {
         double s = 0.0, t = 0.0;
@@ -1817,6 +1890,7 @@ GresCold<T> gres_cold(const HalfArgs<T>& a, const SplitSync* sy) {
         c.chunk_sq = sy->chunk_sq;
         c.chunk_tr = sy->chunk_tr;
         c.newown = static_cast<T*>(sy->newown);
+        c.timeout = sy->timeout;
         c.prof = sy->prof;
         c.lim_slab = sy->lim_slab;
         c.lim_chunk = sy->lim_chunk;
@@ -1839,9 +1913,7 @@ static GresHot<T> gres_hot(const HalfArgs<T>& a, const SplitSync* sy, const Gres
     h.sd_is_var = a.sd_is_var;
     if (sy) {
         h.slabs = sy->slabs;
-        h.counters = sy->counters;
-        h.timeout = sy->timeout;
-        h.ncounters = sy->ncounters;
+        h.qhead = sy->qhead;
     }
     return h;
 }

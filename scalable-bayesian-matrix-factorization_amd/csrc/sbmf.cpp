@@ -339,7 +339,7 @@ struct sbmf_ctx {
     DBuf d_gcold;
     std::vector<unsigned char> h_gcold;
     bool time_kinds = true;   // this sweep records every launch kind's events (else the streaming kind's only)
-    size_t xset_nx = 1, xset_nr = 1;  // set 0's split chunks / rows: set 1's areas follow them
+    size_t xset_nx = 1;  // set 0's split chunks: set 1's areas follow them
     DBuf d_tu, d_ti, d_tr, d_tsum, d_tpart;
     DBuf d_uperm2, d_vperm2, d_uunpack, d_vunpack, d_xrecv;  // multi-GPU residual exchange
     DBuf d_bu, d_bv, d_mbu, d_mbv, d_sbu, d_sbv;  // biases b_i / b_j and their per-row (mu, sigma)
@@ -597,7 +597,7 @@ static void prepare_T(sbmf_ctx* c) {
     }
     // split-row slots of stream set k: the largest over the stages and sides (set 0 and
     // set 1 of a half may run at the same time, so each set has an area of its own)
-    size_t nxk[2] = {0, 0}, nrk[2] = {0, 0};
+    size_t nxk[2] = {0, 0};
     for (Side* sd : {&c->users, &c->items})
         for (auto& g : sd->stg)
             for (int k = 0; k < 2; ++k) {
@@ -605,21 +605,27 @@ static void prepare_T(sbmf_ctx* c) {
                 upload(g->d_stasks[k], S.stasks, st);
                 upload(g->d_xrows[k], S.xrows, st);
                 nxk[k] = std::max<size_t>(nxk[k], S.nxchunk);
-                nrk[k] = std::max<size_t>(nrk[k], S.xrows.size());
             }
     c->xset_nx = std::max<size_t>(nxk[0], 1);
-    c->xset_nr = std::max<size_t>(nrk[0], 1);
     {
-        const size_t nx = c->xset_nx + std::max<size_t>(nxk[1], 1), nr = c->xset_nr + std::max<size_t>(nrk[1], 1);
+        const size_t nx = c->xset_nx + std::max<size_t>(nxk[1], 1);
         // the streaming kernel addresses a set's slabs with 32-bit byte offsets (SplitTask::xrow ...)
         if ((uint64_t)nx * nblk * SLAB_DOUBLES * sizeof(double) >= 0xffffffffull)
             fail(SBMF_E_ARG, "split-row exchange area of %zu chunks at K=%u exceeds 2^32 bytes", nx, c->K);
+        // Every slab word starts as the sentinel (all ones: "not published yet", kernels.hip XSENT)
+        // and is the sentinel again when a streaming launch has run with its k_split_finish: a
+        // chunk resets its slab of block t-1 after reading block t, k_split_finish the last
+        // block's.  An area is used by one launch at a time: set 0 and set 1 have an area each
+        // (they may run side by side), and the launches of one set -- both sides, every stage
+        // (SBMF_STAGES) -- follow each other in stream order (run_half: each set's launches go
+        // to one stream, or the stage ends with the compute stream waiting for the other).
         c->d_xslabs.alloc(nx * nblk * SLAB_DOUBLES * sizeof(double));
+        HIPCHK(hipMemsetAsync(c->d_xslabs.p, 0xff, c->d_xslabs.bytes, st));
         c->d_gcold.alloc((size_t)c->nstages * 6 * sbmf_ctx::kColdSlot);
         c->h_gcold.assign((size_t)c->nstages * 6 * sbmf_ctx::kColdSlot, 0xff);  // nothing uploaded yet
-        // + each set's task-queue head.  Zeroed once here: every streaming launch leaves its set's
-        // area zero again (k_split_finish clears it after k_gres)
-        c->d_xcnt.alloc((nr * nblk + 2 + 3) / 4 * 4 * sizeof(uint32_t));
+        // each set's task-queue head.  Zeroed once here: every streaming launch leaves its set's
+        // zero again (k_split_finish clears it after k_gres)
+        c->d_xcnt.alloc(64 * sizeof(uint32_t));
         HIPCHK(hipMemsetAsync(c->d_xcnt.p, 0, c->d_xcnt.bytes, st));
         c->d_xchunk_sq.alloc(nx * sizeof(double));
         c->d_xchunk_tr.alloc(nx * sizeof(double));
@@ -753,8 +759,8 @@ static void prepare_T(sbmf_ctx* c) {
     c->kprof = std::getenv("SBMF_KPROF") && std::atoi(std::getenv("SBMF_KPROF")) > 0;
     if (c->kprof) {
         if (const char* e = std::getenv("SBMF_KPROF_SET")) c->kprof_set = std::atoi(e) ? 1 : 0;
-        c->d_kprof.alloc(96 * sizeof(unsigned long long));
-        HIPCHK(hipMemset(c->d_kprof.p, 0, 96 * sizeof(unsigned long long)));
+        c->d_kprof.alloc(128 * sizeof(unsigned long long));
+        HIPCHK(hipMemset(c->d_kprof.p, 0, 128 * sizeof(unsigned long long)));
     }
     for (hipEvent_t& e : c->kevs) event_destroy(e);
     for (hipEvent_t& e : c->sev) event_destroy(e);
@@ -790,10 +796,9 @@ static void build_stream_tasks(const Side& s, Side::StreamSet& S, const std::vec
         if (nch > gres)
             fail(SBMF_E_ARG, "row %u has %u ratings: more than %u co-resident chunks of %u", r, n, gres, cmax);
         if (nch == 1) {
-            S.stasks.push_back(SplitTask{r, s.ptr[r], n, 1, 0, 0, 0, 0, 0, 0, {0, 0}});
+            S.stasks.push_back(SplitTask{r, s.ptr[r], n, 1, 0, 0, 0, 0, 0, {0, 0, 0}});
         } else {
             const uint32_t slab0 = S.nxchunk;
-            const uint32_t cnt0 = (uint32_t)S.xrows.size() * nblk;
             const uint32_t per = (n + nch - 1) / nch;
             // byte offsets of the row's slabs in the set's area (set_data checks the area < 2^32 bytes)
             const uint64_t xstr = (uint64_t)nblk * SLAB_DOUBLES * sizeof(double), xrow = (uint64_t)slab0 * xstr;
@@ -801,8 +806,8 @@ static void build_stream_tasks(const Side& s, Side::StreamSet& S, const std::vec
                 fail(SBMF_E_ARG, "split-row exchange area exceeds 2^32 bytes at row %u", r);
             for (uint32_t c = 0; c < nch; ++c) {
                 const uint32_t b = c * per, e = std::min(n, b + per);
-                S.stasks.push_back(SplitTask{r, s.ptr[r] + b, e - b, nch, c, slab0, cnt0, (uint32_t)xrow,
-                                             (uint32_t)(xrow + c * xstr), (uint32_t)xstr, {0, 0}});
+                S.stasks.push_back(SplitTask{r, s.ptr[r] + b, e - b, nch, c, slab0, (uint32_t)xrow,
+                                             (uint32_t)(xrow + c * xstr), (uint32_t)xstr, {0, 0, 0}});
             }
             S.xrows.push_back(SplitRow{r, slab0, nch, 0});
             S.nxchunk += nch;
@@ -1144,12 +1149,11 @@ static void run_half(sbmf_ctx* c, bool users, uint32_t stage, hipEvent_t start =
                 const Side::StreamSet& S = g.ss[set];
                 if (S.stasks.empty()) continue;
                 const hipStream_t ss = sov && set == 0 ? c->sto : st;
-                const size_t ox = set ? c->xset_nx : 0, orow = set ? c->xset_nr : 0;
+                const size_t ox = set ? c->xset_nx : 0;
                 SplitSync sy{};
                 sy.nblk = (c->K + 15) / 16;
                 sy.slabs = c->d_xslabs.as<double>() + ox * sy.nblk * SLAB_DOUBLES;
-                sy.counters = c->d_xcnt.as<uint32_t>() + (set ? orow * sy.nblk + 1 : 0);
-                sy.ncounters = (uint32_t)S.xrows.size() * sy.nblk;
+                sy.qhead = c->d_xcnt.as<uint32_t>() + 32 * set;  // a 128-byte line each
                 sy.chunk_sq = c->d_xchunk_sq.as<double>() + ox;
                 sy.chunk_tr = c->d_xchunk_tr.as<double>() + ox;
                 sy.newown = c->d_xnewown.as<T>() + ox * c->Kp;
@@ -1627,7 +1631,7 @@ static void run_sweeps_T(sbmf_ctx* c, uint32_t nsweeps, sbmf_sweep_cb cb, void* 
         uint32_t split_timeout;
         std::memcpy(&split_timeout, res8 + RES_TIMEOUT, sizeof(split_timeout));
         if (c->kprof) {
-            unsigned long long h[96];
+            unsigned long long h[128];
             HIPCHK(hipMemcpy(h, c->d_kprof.p, sizeof(h), hipMemcpyDeviceToHost));
             HIPCHK(hipMemset(c->d_kprof.p, 0, sizeof(h)));
             static const char* gn[7] = {"setup", "load+mfma", "barrier", "reduce", "solve+handoff", "e-update",
@@ -1647,6 +1651,11 @@ static void run_sweeps_T(sbmf_ctx* c, uint32_t nsweeps, sbmf_sweep_cb cb, void* 
             for (int sd = 0; sd < 2; ++sd) {
                 const Side& S = sd ? c->items : c->users;
                 double tot = 0;
+                // phase 4 (cross-wave sum + split-row exchange) comes in three parts: the sum and
+                // the publish [96 + 2 sd], the publish to the first valid batch [97 + 2 sd], and
+                // the rest (read + sum) in slot 4; per class at [100 + 6 sd + 2 cl]
+                const unsigned long long x7 = h[96 + 2 * sd], x8 = h[97 + 2 * sd], x4 = h[8 * sd + 4];
+                h[8 * sd + 4] += x7 + x8;
                 for (int k = 0; k < 7; ++k) tot += (double)h[8 * sd + k];
                 if (tot == 0) continue;
                 std::fprintf(stderr, "[kprof] sweep %u gres %s (grid %u, %zu tasks, wave-0 Mcycles per WG):", s_cur,
@@ -1655,14 +1664,20 @@ static void run_sweeps_T(sbmf_ctx* c, uint32_t nsweeps, sbmf_sweep_cb cb, void* 
                 for (int k = 0; k < 7; ++k)
                     std::fprintf(stderr, " %s %.3f (%.0f%%)", nm[k], (double)h[8 * sd + k] / S.stg[0]->ss[c->kprof_set].sgrid / 1e6,
                                  100.0 * (double)h[8 * sd + k] / tot);
-                std::fprintf(stderr, "\n");
+                std::fprintf(stderr, "\n[kprof]   xwave+xchg = xwave+publish %.3f + to-first-valid %.3f + read+sum %.3f\n",
+                             (double)x7 / S.stg[0]->ss[c->kprof_set].sgrid / 1e6, (double)x8 / S.stg[0]->ss[c->kprof_set].sgrid / 1e6,
+                             (double)x4 / S.stg[0]->ss[c->kprof_set].sgrid / 1e6);
                 static const char* cn[3] = {"whole rows", "2-16 chunks", ">16 chunks"};
                 for (int cl = 0; cl < 3; ++cl) {
-                    const unsigned long long* hc = h + 32 + 24 * sd + 8 * cl;
+                    unsigned long long* hc = h + 32 + 24 * sd + 8 * cl;
                     if (!hc[7]) continue;
+                    const unsigned long long* hx = h + 100 + 6 * sd + 2 * cl;
+                    const unsigned long long c4 = hc[4];
+                    hc[4] += hx[0] + hx[1];
                     std::fprintf(stderr, "[kprof]   %s: %llu tasks, kcycles per task:", cn[cl], hc[7]);
                     for (int k = 0; k < 7; ++k) std::fprintf(stderr, " %s %.1f", nm[k], (double)hc[k] / hc[7] / 1e3);
-                    std::fprintf(stderr, "\n");
+                    std::fprintf(stderr, " (xwave+publish %.1f, to-first-valid %.1f, read+sum %.1f)\n", (double)hx[0] / hc[7] / 1e3,
+                                 (double)hx[1] / hc[7] / 1e3, (double)c4 / hc[7] / 1e3);
                 }
             }
         }
