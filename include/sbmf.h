@@ -284,6 +284,59 @@ typedef struct sbmf_timing {
 } sbmf_timing;
 int sbmf_get_timing(sbmf_ctx* ctx, sbmf_timing* t);
 
+/* --- posterior top-N for a watch list of users ----------------------------------------------- */
+/* Not a reference interface: the reference scores only the test pairs it was
+ * given (gibbs_sbpmf_final.cpp:539-563).  A watch list is a caller-chosen set
+ * of users whose score against EVERY item is tracked inside the chain: after
+ * each collected sweep s the sampler adds score_s(w, j) = u_s[users[w]] . v_s[j]
+ * (+ b0 + b_u + b_j with the biased quirk sets, as the test prediction adds
+ * them) and its square to device-resident f64 sums, so the posterior mean is
+ * the mean over sweeps of u_s . v_s, not the product of mean factors.  The
+ * products and sums are f64 in both precisions (an F32 context's table values
+ * are widened on load), every element is summed in a fixed order without
+ * atomics, and the sampler's chain is untouched: a context with a watch list
+ * draws bit for bit what it draws without one.
+ * Scope: the SBPMF sampler (SBMF_METHOD_MCMC, every quirk set) on one rank.
+ * Out of scope here, each refused with SBMF_E_STATE and a message naming the
+ * reason: the VB, libFM-MCMC and ALS learners; a context that joined a
+ * communicator; a virtual rank; and reading results before any sweep was
+ * accumulated.
+ *
+ * sbmf_watch_users: register (or replace) the list.  After sbmf_prepare, also
+ * between sbmf_run calls.  Allocates and zeroes two [n][Jp] f64 accumulators
+ * (Jp = num_items rounded up to 16) and restarts the list's own count n_w of
+ * accumulated sweeps; n = 0 drops the list and frees them.  flags bit 0: clamp
+ * each sweep's score to the context's [clamp_lo, clamp_hi] before accumulating,
+ * as the test prediction is clamped (default: unclamped, which is what ranking
+ * wants -- clamped scores saturate and tie).  Ids may repeat (duplicate rows).
+ * An id >= num_users is SBMF_E_ARG; a failed allocation SBMF_E_NOMEM with the
+ * byte count in the message (the list is then dropped).  Memory: 16 n Jp bytes
+ * -- every user of ML-20M would need 59 GB, which is why the list is the
+ * caller's.  sbmf_set_factors leaves the sums alone. */
+int sbmf_watch_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t flags);
+/* The full row of watched user w (index into the list): mean[j] = S1 / n_w,
+ * stdev[j] = sqrt(max(0, S2 / n_w - mean^2)), j < num_items: the population
+ * spread over the n_w sweeps collected since registration.  The reference's
+ * running-mean quirk (divide by sweep + 1, burn-in included: sbmf_config.average)
+ * is NOT reproduced here; with clamping on, mean differs from sbmf_predict only
+ * when burnin > 0 under that default divisor (or when the list was registered
+ * after the first collected sweep).  stdev may be NULL. */
+int sbmf_watch_scores(sbmf_ctx* ctx, uint32_t w, double* mean, double* stdev);
+/* Per watched user the topn (1..1024, else SBMF_E_ARG) items with the largest
+ * key mean - risk * stdev, formed in IEEE double arithmetic from exactly the
+ * values sbmf_watch_scores returns: risk = 0 ranks by posterior mean, risk > 0
+ * by a lower confidence bound.  Order: key descending, ties by ascending item
+ * id -- exact and deterministic.  Items the user rated in the training set are
+ * left out unless flags bit 0 is set.  items / mean / stdev: [n][topn], row w
+ * for users[w]; slots past the number of candidates hold item 0xffffffff and
+ * NaN.  stdev may be NULL. */
+int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                   double* stdev);
+/* Device time (HIP events), ms: the last collected sweep's scoring launch and
+ * the last sbmf_recommend's selection (mask + select kernels); 0 before the
+ * first.  A call of its own because sbmf_timing keeps its size (ABI 2). */
+int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select);
+
 /* --- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------------------- */
 /* 128-byte RCCL unique id, produced by rank 0 and shared by the launcher. */
 int sbmf_comm_unique_id(uint8_t id[128]);

@@ -34,6 +34,7 @@
 #include "kernels.h"
 #include "rng.h"
 #include "fmm.h"
+#include "recommend.h"
 #include "vbo.h"
 
 namespace {
@@ -368,6 +369,15 @@ struct sbmf_ctx {
     double* h_pinned = nullptr;  // pinned staging for z streams
     size_t h_pinned_bytes = 0, h_pre_bytes = 0, h_io_bytes = 0;
     sbmf_timing timing{};
+    // Watch list (sbmf_watch_users): the watched users' ids and the running first / second
+    // moments of their scores against every item, [wn][wJp] doubles each, added to after every
+    // collected sweep (recommend.hip).  Nothing here exists while no list is registered.
+    uint32_t wn = 0, wJp = 0;
+    uint32_t wcount = 0;   // sweeps accumulated since the list was registered (n_w)
+    int wclamp = 0;        // flags bit 0: scores clamped like the test prediction
+    DBuf d_wusers, d_wS1, d_wS2;
+    hipEvent_t wev[4] = {};  // the scoring launch [begin, end], the last selection [begin, end]
+    bool wtimed_score = false, wtimed_select = false;
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
     FMLearner* fm = nullptr;  // -method mcmc --order libfm / als (fmm.cpp)
     ~sbmf_ctx();
@@ -1531,6 +1541,19 @@ static void run_sweeps_T(sbmf_ctx* c, uint32_t nsweeps, sbmf_sweep_cb cb, void* 
             }
             if (cf.eval_train)
                 HIPCHK(launch_sum(c->d_rowtr_v.as<double>(), c->J, d_res + RES_TRSQ, scratch + c->scratch_half, se));
+            // the watch list's scores of this sample (only reads U, V and the biases, like the
+            // test prediction, and shares its ordering against the next sweep's user half)
+            if (c->wn && collect) {
+                HIPCHK(hipEventRecord(c->wev[0], se));
+                HIPCHK(launch_watch_accum<T>(c->d_wusers.as<uint32_t>(), c->wn, c->d_U.as<T>(), c->d_V.as<T>(), c->J,
+                                             c->Kp, c->bias ? c->d_bu.as<double>() : nullptr, c->d_bv.as<double>(),
+                                             c->b0, c->wclamp, c->lo, c->hi, c->d_wS1.as<double>(),
+                                             c->d_wS2.as<double>(), se));
+                HIPCHK(hipEventRecord(c->wev[1], se));
+                c->wcount++;
+                c->wtimed_score = true;
+                c->timing.n_launch++;
+            }
             HIPCHK(hipEventRecord(c->ev[6], se));
         };
         if (par_eval) {
@@ -1716,6 +1739,7 @@ sbmf_ctx::~sbmf_ctx() {
     for (hipEvent_t& e : tsev) event_destroy(e);
     for (hipEvent_t& e : cev) event_destroy(e);
     for (hipEvent_t& e : oev) event_destroy(e);
+    for (hipEvent_t& e : wev) event_destroy(e);
     event_destroy(hev);
     stream_destroy(sto);
     stream_destroy(sto2);
@@ -2230,6 +2254,143 @@ int sbmf_get_dims(sbmf_ctx* ctx, uint32_t* nu, uint32_t* ni, uint64_t* ntr, uint
     if (ni) *ni = ctx->J;
     if (ntr) *ntr = ctx->tu.size();
     if (nte) *nte = ctx->su.size();
+    API_END(ctx)
+}
+
+// --- watch list ------------------------------------------------------------------------------
+// The learners and schedules the watch list covers; everything else is SBMF_E_STATE.
+static void watch_scope(const sbmf_ctx* c, const char* fn) {
+    if (c->cfg.method != SBMF_METHOD_MCMC)
+        sbmf::fail(SBMF_E_STATE, "%s: the watch list is offered by the SBPMF sampler (SBMF_METHOD_MCMC) only; this "
+                                 "context runs the %s learner", fn,
+                   c->cfg.method == SBMF_METHOD_VB ? "online VB" : c->cfg.method == SBMF_METHOD_ALS ? "ALS" : "libFM MCMC");
+    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no watch list there", fn);
+    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
+        sbmf::fail(SBMF_E_STATE, "%s: the watch list runs on one rank; this context joined a communicator", fn);
+    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+}
+static void watch_drop(sbmf_ctx* c) {
+    c->d_wusers.release();
+    c->d_wS1.release();
+    c->d_wS2.release();
+    for (hipEvent_t& e : c->wev) sbmf::event_destroy(e);
+    c->wn = c->wJp = c->wcount = 0;
+    c->wclamp = 0;
+    c->wtimed_score = c->wtimed_select = false;
+}
+// the accumulated sweeps' work is done (the scoring launch runs on the evaluation's stream,
+// which the compute stream waits for before the sweep's results are copied)
+static void watch_ready(sbmf_ctx* c, const char* fn) {
+    if (!c->wn) sbmf::fail(SBMF_E_STATE, "%s: no watch list registered (sbmf_watch_users)", fn);
+    if (!c->wcount) sbmf::fail(SBMF_E_STATE, "%s: no sweep accumulated since the watch list was registered", fn);
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->sto));
+    HIPCHK(hipStreamSynchronize(c->st));
+}
+
+int sbmf_watch_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t flags) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    watch_scope(ctx, "sbmf_watch_users");
+    if (n && !users) sbmf::fail(SBMF_E_ARG, "null user list with n > 0");
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_watch_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
+    for (uint32_t w = 0; w < n; ++w)
+        if (users[w] >= ctx->I)
+            sbmf::fail(SBMF_E_ARG, "sbmf_watch_users: users[%u] = %u is not below the %u users", w, users[w], ctx->I);
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->sto));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    watch_drop(ctx);
+    if (n == 0) return SBMF_OK;
+    try {
+        const uint32_t Jp = sbmf::watch_jp(ctx->J);
+        const size_t bytes = (size_t)n * Jp * sizeof(double);
+        ctx->d_wS1.alloc(bytes);
+        ctx->d_wS2.alloc(bytes);
+        ctx->d_wusers.alloc((size_t)n * sizeof(uint32_t));
+        for (hipEvent_t& e : ctx->wev) sbmf::event_create(&e);
+        HIPCHK(hipMemsetAsync(ctx->d_wS1.p, 0, bytes, ctx->st));
+        HIPCHK(hipMemsetAsync(ctx->d_wS2.p, 0, bytes, ctx->st));
+        HIPCHK(hipMemcpyAsync(ctx->d_wusers.p, users, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->st));
+        HIPCHK(hipStreamSynchronize(ctx->st));
+        ctx->wn = n;
+        ctx->wJp = Jp;
+        ctx->wclamp = (int)(flags & 1u);
+    } catch (...) {
+        watch_drop(ctx);
+        throw;
+    }
+    API_END(ctx)
+}
+
+int sbmf_watch_scores(sbmf_ctx* ctx, uint32_t w, double* mean, double* stdev) {
+    API_BEGIN
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    watch_scope(ctx, "sbmf_watch_scores");
+    watch_ready(ctx, "sbmf_watch_scores");
+    if (w >= ctx->wn) sbmf::fail(SBMF_E_ARG, "sbmf_watch_scores: row %u of a watch list of %u", w, ctx->wn);
+    const uint32_t J = ctx->J;
+    sbmf::DBuf tmp;
+    tmp.alloc((size_t)2 * J * sizeof(double));
+    double* d = tmp.as<double>();
+    HIPCHK(sbmf::launch_watch_moments(ctx->d_wS1.as<double>() + (size_t)w * ctx->wJp,
+                                      ctx->d_wS2.as<double>() + (size_t)w * ctx->wJp, J, (double)ctx->wcount, d, d + J,
+                                      ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    API_END(ctx)
+}
+
+int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                   double* stdev) {
+    API_BEGIN
+    if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    watch_scope(ctx, "sbmf_recommend");
+    if (topn < 1 || topn > 1024) sbmf::fail(SBMF_E_ARG, "sbmf_recommend: topn %u is not in 1..1024", topn);
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_recommend: unknown flags 0x%x (bit 0 = keep rated items)", flags & ~1u);
+    if (!(risk == risk)) sbmf::fail(SBMF_E_ARG, "sbmf_recommend: risk is NaN");
+    watch_ready(ctx, "sbmf_recommend");
+    const uint32_t n = ctx->wn, J = ctx->J, Jw = sbmf::watch_jw(J);
+    const size_t slots = (size_t)n * topn;
+    sbmf::DBuf d_it, d_ms, d_mask;
+    d_it.alloc(slots * sizeof(uint32_t));
+    d_ms.alloc(2 * slots * sizeof(double));
+    const bool exclude = !(flags & 1u);
+    if (exclude) d_mask.alloc((size_t)n * Jw * sizeof(uint32_t));
+    hipStream_t st = ctx->st;
+    HIPCHK(hipEventRecord(ctx->wev[2], st));
+    if (exclude) {
+        HIPCHK(hipMemsetAsync(d_mask.p, 0, (size_t)n * Jw * sizeof(uint32_t), st));
+        HIPCHK(sbmf::launch_watch_mask(ctx->d_wusers.as<uint32_t>(), n, ctx->d_uptr.as<uint32_t>(),
+                                       ctx->d_upart.as<uint32_t>(), d_mask.as<uint32_t>(), Jw, st));
+    }
+    HIPCHK(sbmf::launch_watch_select(n, ctx->d_wS1.as<double>(), ctx->d_wS2.as<double>(), J, (double)ctx->wcount, risk,
+                                     exclude ? d_mask.as<uint32_t>() : nullptr, topn, d_it.as<uint32_t>(),
+                                     d_ms.as<double>(), d_ms.as<double>() + slots, st));
+    HIPCHK(hipEventRecord(ctx->wev[3], st));
+    HIPCHK(hipStreamSynchronize(st));
+    ctx->wtimed_select = true;
+    HIPCHK(hipMemcpy(items, d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mean, d_ms.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d_ms.as<double>() + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+    API_END(ctx)
+}
+
+int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    watch_scope(ctx, "sbmf_watch_timing");
+    if (!ctx->wn) sbmf::fail(SBMF_E_STATE, "sbmf_watch_timing: no watch list registered (sbmf_watch_users)");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if (ms_score) {
+        *ms_score = 0.0;
+        if (ctx->wtimed_score) {
+            HIPCHK(hipEventSynchronize(ctx->wev[1]));
+            *ms_score = sbmf::ev_ms(ctx->wev[0], ctx->wev[1]);
+        }
+    }
+    if (ms_select) *ms_select = ctx->wtimed_select ? sbmf::ev_ms(ctx->wev[2], ctx->wev[3]) : 0.0;
     API_END(ctx)
 }
 

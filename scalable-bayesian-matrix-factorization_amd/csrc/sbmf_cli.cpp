@@ -10,6 +10,8 @@
 // and the file test_rmse_<k0><k1><K>_<method> (truncated at start, one
 // running-mean test RMSE per line, :57-62,146); -out writes one averaged
 // prediction per test line (libfm.cpp:629-634).
+// Beyond libFM: -recommend / -rec_users / -rec_topn / -rec_risk write the SBPMF sampler's
+// posterior top-N items for a list of users (sbmf_watch_users / sbmf_recommend).
 // Differences, by design: -seed is honoured (libfm.cpp:124 ignores it); on
 // error the exit code is 1 (the reference prints "ERROR" and returns 0).
 #include <algorithm>
@@ -379,6 +381,14 @@ int main(int argc, char** argv) {
         cl.reg("split_chunk", "streaming task size; longer rows are split into chunks on several workgroups; default: "
                               "the register capacity of the workgroup shape (512 / 1024 / 2048 f64 ratings for 4 / 8 / "
                               "16 waves), larger values are capped to it");
+        // posterior top-N for a list of users (sbmf_watch_users / sbmf_recommend)
+        cl.reg("recommend", "filename for output: per user of -rec_users the -rec_topn unrated items with the largest "
+                            "posterior mean score (less -rec_risk stdevs), one 'user<TAB>item<TAB>mean<TAB>stdev' line "
+                            "each, ids as in the input files; the SBPMF sampler only (-method mcmc -order sbpmf); on "
+                            "libFM input the item offset then defaults to libFM's num_user");
+        cl.reg("rec_users", "filename with one user id per line [MANDATORY with -recommend]");
+        cl.reg("rec_topn", "items per user, 1..1024; default=10");
+        cl.reg("rec_risk", "rank by mean - x * stdev (a lower confidence bound for x > 0); default=0");
         if (cl.has("help") || argc == 1) {
             cl.print_help();
             return leave(0);
@@ -388,6 +398,16 @@ int main(int argc, char** argv) {
         if (task != "r") throw std::runtime_error("only -task r (regression) is supported by the SBPMF sampler");
         const std::string method = cl.get("method", "mcmc");
         const bool vb = method == "vb" || method == "vb_online";
+        const bool rec = cl.has("recommend");
+        const char* rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
+        if (rec && cl.get("recommend", "").empty()) throw std::runtime_error("-recommend needs a file name");
+        if (rec && cl.get("rec_users", "").empty())
+            throw std::runtime_error("-recommend needs -rec_users <file> (one user id per line)");
+        if (!rec && (cl.has("rec_users") || cl.has("rec_topn") || cl.has("rec_risk")))
+            throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
+        if (rec && method != "mcmc") throw std::runtime_error(rec_refusal);  // before any file is opened
+        const long rec_topn = cl.getl("rec_topn", 10);
+        if (rec && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
         const std::string fmt = cl.get("format", "auto");
         if (fmt != "auto" && fmt != "triple" && fmt != "libfm" && fmt != "binary")
             throw std::runtime_error("unknown -format " + fmt);
@@ -406,6 +426,7 @@ int main(int argc, char** argv) {
         const bool biased = q == "bias2" || q == "bias22";
         // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
         const bool lfm = als || (method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
+        if (rec && lfm) throw std::runtime_error(rec_refusal);
         if (method != "mcmc" && !vb && !als)
             throw std::runtime_error("-method " + method + " is not supported (use mcmc, als or vb)");
         if (!cl.has("train") || !cl.has("test")) throw std::runtime_error("-train and -test are mandatory");
@@ -489,7 +510,24 @@ int main(int argc, char** argv) {
         // (libfm.cpp:219-221,263-265,375) and num_all_attribute = max feature id + 1 (:328).
         // With one user and one item feature per line that is the users-first layout with
         // item offset num_user, so no flag is needed (-item_offset overrides it).
-        if ((lfm || vb) && libfm_input && !cl.has("item_offset")) off = users_first_offset(tr, te);
+        // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
+        if ((lfm || vb || rec) && libfm_input && !cl.has("item_offset")) off = users_first_offset(tr, te);
+        std::vector<uint32_t> rec_ids;
+        if (rec) {
+            std::ifstream f(cl.get("rec_users", ""));
+            if (!f.is_open()) throw std::runtime_error("Unable to open file " + cl.get("rec_users", ""));
+            std::string line;
+            while (std::getline(f, line)) {
+                const size_t p = line.find_first_not_of(" \t\r");
+                if (p == std::string::npos || line[p] == '#') continue;
+                char* end = nullptr;
+                const unsigned long long v = std::strtoull(line.c_str() + p, &end, 10);
+                if (end == line.c_str() + p || v > 0xfffffffeull)
+                    throw std::runtime_error("-rec_users: cannot read a user id from '" + line + "'");
+                rec_ids.push_back((uint32_t)v);
+            }
+            if (rec_ids.empty()) throw std::runtime_error("-rec_users: " + cl.get("rec_users", "") + " lists no user");
+        }
 
         sbmf_ctx* ctx = nullptr;
         if (sbmf_create(&cfg, &ctx) != SBMF_OK) throw std::runtime_error(sbmf_last_global_error());
@@ -538,7 +576,26 @@ int main(int argc, char** argv) {
             rs.rlog = &rlog;
         }
         rs.verbosity = (int)cl.getl("verbosity", 0);
+        if (rec) chk(sbmf_watch_users(ctx, (uint32_t)rec_ids.size(), rec_ids.data(), 0));
         chk(sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
+        if (rec) {
+            const size_t topn = (size_t)rec_topn, slots = rec_ids.size() * topn;
+            std::vector<uint32_t> it(slots);
+            std::vector<double> mean(slots), sd(slots);
+            chk(sbmf_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
+            FILE* f = std::fopen(cl.get("recommend", "").c_str(), "w");
+            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend", ""));
+            // ids as in the input files: on libFM input the item's feature id
+            const uint64_t ioff = libfm_input ? off : 0;
+            for (size_t w = 0; w < rec_ids.size(); ++w)
+                for (size_t k = 0; k < topn; ++k) {
+                    const size_t x = w * topn + k;
+                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
+                    std::fprintf(f, "%u\t%llu\t%.17g\t%.17g\n", rec_ids[w], (unsigned long long)(it[x] + ioff), mean[x],
+                                 sd[x]);
+                }
+            std::fclose(f);
+        }
         if (cl.has("out") && !cl.get("out", "").empty()) {
             std::vector<double> pred(nte);
             chk(sbmf_predict(ctx, pred.data()));

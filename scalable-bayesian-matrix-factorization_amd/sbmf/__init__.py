@@ -347,6 +347,45 @@ class FMLearnSBPMF:
         self._check(lib.sbmf_get_timing(self.ctx, C.byref(t)))
         return t
 
+    # -- posterior top-N for a watch list of users (include/sbmf.h; not a reference interface)
+    def watch(self, users, clamp=False):
+        """Track the score of every item for these users (ids may repeat) from the next
+        sweep on: sbmf_watch_users.  ``clamp``: clamp each sweep's score like the test
+        prediction.  An empty list drops the watch and frees its device buffers."""
+        users = _u32(users).ravel()
+        self._check(lib.sbmf_watch_users(self.ctx, len(users), _ptr(users, C.c_uint32), 1 if clamp else 0))
+        self._n_watch = len(users)
+
+    def watch_scores(self, w):
+        """(mean, stdev) of watched user ``w`` (index into the list) over the sweeps
+        collected since ``watch``, one value per item."""
+        _, ni, _, _ = self.dims()
+        mean, sd = np.zeros(ni), np.zeros(ni)
+        self._check(lib.sbmf_watch_scores(self.ctx, int(w), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        return mean, sd
+
+    def recommend(self, topn=10, exclude_rated=True, risk=0.0):
+        """Per watched user the ``topn`` items with the largest mean - risk * stdev (ties by
+        ascending item id), without the items the user rated in training unless
+        ``exclude_rated`` is False.  Returns (items int64 [n, topn] with -1 in empty
+        slots, mean, stdev); empty slots hold NaN."""
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        n, t = getattr(self, "_n_watch", 0), int(topn)
+        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
+        self._check(lib.sbmf_recommend(self.ctx, t, 0 if exclude_rated else 1, float(risk), _ptr(items, C.c_uint32),
+                                       _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = items[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def watch_timing(self):
+        """Device ms of the last sweep's scoring launch and of the last selection."""
+        a, b = C.c_double(), C.c_double()
+        self._check(lib.sbmf_watch_timing(self.ctx, C.byref(a), C.byref(b)))
+        return {"ms_score": a.value, "ms_select": b.value}
+
     def close(self):
         if self.ctx is not None:
             lib.sbmf_destroy(self.ctx)

@@ -14,6 +14,7 @@ import numpy as np
 SHAPES = {
     # name: (users, items, total ratings, max user degree, max item degree)
     "ml-100k": (943, 1682, 100_000, 737, 583),
+    "ml-2k": (2000, 3000, 150_000, 600, 1200),  # a reduced MovieLens shape for quick multi-block tests
     "ml-1m": (6040, 3706, 1_000_209, 2314, 3428),
     "ml-10m": (69878, 10677, 10_000_054, 7359, 34864),
     "ml-20m": (138493, 26744, 20_000_263, 9254, 67310),
