@@ -337,6 +337,67 @@ int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, ui
  * first.  A call of its own because sbmf_timing keeps its size (ABI 2). */
 int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select);
 
+/* --- fold-in list: posterior top-N for users outside the training set ------------------------ */
+/* Guests are users who have no row in U: they arrived after the chain started,
+ * and the caller gives their ratings instead of an id.  Given a sweep's item
+ * factors V_s, the user-side hyperparameters and tau, a guest's factor row has
+ * exactly the conditional the user half draws its rows from; drawing it once per
+ * sweep beside the chain gives a posterior sample of the guest's factors.  The
+ * guests' ratings never feed back: with or without a list, U, V, the
+ * hyperparameters, the predictions and the watch list's results are bit for bit
+ * the same.  Scores, moments and the top-N are the watch list's, kept in sums
+ * of the fold-in list's own; both lists may be registered at once.
+ *
+ * The draw, after every sweep's item half since registration (burn-in included),
+ * starting from the row the previous sweep left (zero at registration), with the
+ * sigma_u, mu_u and tau the sweep's user half used, all in f64 (an F32 context's V
+ * is widened on load, the row rounded once on store):
+ *   e_j = r_j - G[g] . V_s[item_j]             over the guest's ratings, then for k = 0..K-1:
+ *   P = sum_j v_jk^2,  Q = sum_j v_jk (e_j + v_jk u_k)
+ *   var = 1 / (sigma_k + tau P),  mean = var (tau Q + sigma_k mu_k)
+ *   u_k' = mean + s z_k,  s = var under the quirk sets final / sbpmf2 (the reference's
+ *                          variance-as-stdev quirk), sqrt(var) under none
+ *   e_j += v_jk (u_k - u_k')
+ * z_k = sbmf_philox_normals(seed, absolute sweep index, 7, g, K)[k] in both RNG
+ * modes (to the last bits of the device's log / sincos, as for the other tags);
+ * the reference-mode host stream is not touched.  A guest without ratings is
+ * drawn from N(mu_u, .): the cold start.  A rerun gives bit-identical rows and sums.
+ *
+ * Scope: the SBPMF sampler with the unbiased quirk sets, one rank, both
+ * precisions, both RNG modes.  SBMF_E_STATE with a message naming the reason:
+ * the biased quirk sets (a guest bias would need a draw of its own); the VB,
+ * libFM-MCMC and ALS learners; a context that joined a communicator; a virtual
+ * rank; reading results before a sweep was drawn (factors) or accumulated
+ * (scores, top-N).
+ *
+ * sbmf_foldin_users: register (or replace) the list of n guests, a CSR:
+ * ptr[n + 1], guest g's ratings are items[ptr[g] .. ptr[g + 1]) (each below
+ * num_items; a repeated item counts as separate ratings) with ratings[] beside
+ * them; a guest may have none.  After sbmf_prepare, also between sbmf_run calls.
+ * Allocates the guest table ([n + 2][Kp] in the context's precision), a residual
+ * scratch of ptr[n] - ptr[0] doubles and two [n][Jp] f64 accumulators, copies the
+ * CSR, and restarts the rows (zero) and counts; n = 0 drops the list and frees
+ * everything.  flags bit 0: clamp each sweep's score as sbmf_watch_users does.
+ * SBMF_E_ARG: an item id >= num_items, a decreasing ptr, unknown flags.
+ * SBMF_E_NOMEM with the byte count in the message on a failed allocation (the
+ * list is then dropped). */
+int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                      uint32_t flags);
+/* The current sample's guest rows, rows[n][K] (the last sweep's draw). */
+int sbmf_foldin_factors(sbmf_ctx* ctx, double* rows);
+/* Guest g's row of posterior means and standard deviations over the sweeps
+ * collected since registration; definitions as sbmf_watch_scores.  stdev may be NULL. */
+int sbmf_foldin_scores(sbmf_ctx* ctx, uint32_t g, double* mean, double* stdev);
+/* sbmf_recommend for the guests: key, order, tie rule, outputs [n][topn] and
+ * empty slots as there.  "Rated" means the guest's own items (left out unless
+ * flags bit 0 is set); a guest without ratings excludes nothing. */
+int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                          double* stdev);
+/* Device time (HIP events), ms: the last sweep's draw, the last collected
+ * sweep's scoring launch, the last sbmf_foldin_recommend's selection; 0 before
+ * the first. */
+int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select);
+
 /* --- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------------------- */
 /* 128-byte RCCL unique id, produced by rank 0 and shared by the launcher. */
 int sbmf_comm_unique_id(uint8_t id[128]);

@@ -141,7 +141,7 @@ SBMF_HD P4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uin
 
 // Stream tags (counter word 2, low byte).
 enum : uint32_t { TAG_USERS = 0, TAG_ITEMS = 1, TAG_HOST = 2, TAG_INIT_U = 3, TAG_INIT_V = 4, TAG_BIAS_U = 5,
-                  TAG_BIAS_V = 6 };
+                  TAG_BIAS_V = 6, TAG_GUEST = 7 /* fold-in rows (foldin.hip), row = the guest's index */ };
 static const uint32_t PHILOX_SALT = 0x53424d46u;  // "SBMF"
 
 // Two N(0,1) variates (Box-Muller, 53-bit uniforms): normal indices 2*pair

@@ -34,6 +34,7 @@
 #include "kernels.h"
 #include "rng.h"
 #include "fmm.h"
+#include "foldin.h"
 #include "recommend.h"
 #include "vbo.h"
 
@@ -378,6 +379,23 @@ struct sbmf_ctx {
     DBuf d_wusers, d_wS1, d_wS2;
     hipEvent_t wev[4] = {};  // the scoring launch [begin, end], the last selection [begin, end]
     bool wtimed_score = false, wtimed_select = false;
+    // Fold-in list (sbmf_foldin_users): guests given by their ratings (a CSR on the device),
+    // their factor rows G [fn + 2][Kp] in the tables' type (row fn zero, row fn + 1 slack: the
+    // tables' layout, so the watch list's scoring kernel reads it as a U), drawn after every
+    // sweep's item half (foldin.hip), and the moments of their scores [fn][fJp] as the watch
+    // list keeps them.  d_fhyp is the list's own [sig_u | mu_u] (2 Kp doubles) of the sweep
+    // being evaluated: d_hyper may already hold the next sweep's (stage_hyper).  d_fident is
+    // 0..fn-1 (the scoring kernel's user list), d_forder the guests by falling length.  Nothing
+    // here exists while no list is registered.
+    uint32_t fn = 0, fJp = 0;
+    uint32_t fdrawn = 0;   // sweeps drawn since the list was registered
+    uint32_t fcount = 0;   // of those, the collected ones: accumulated into the sums
+    int fclamp = 0;
+    DBuf d_fptr, d_fitems, d_fratings, d_fident, d_forder, d_fG, d_fE, d_fhyp, d_fS1, d_fS2;
+    double* h_fhyp = nullptr;  // pinned staging of d_fhyp
+    size_t h_fhyp_bytes = 0;
+    hipEvent_t fev[5] = {};  // hyper copy done = draw begin, draw end = scoring begin, scoring end; selection [begin, end]
+    bool ftimed_draw = false, ftimed_score = false, ftimed_select = false;
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
     FMLearner* fm = nullptr;  // -method mcmc --order libfm / als (fmm.cpp)
     ~sbmf_ctx();
@@ -1554,6 +1572,36 @@ static void run_sweeps_T(sbmf_ctx* c, uint32_t nsweeps, sbmf_sweep_cb cb, void* 
                 c->wtimed_score = true;
                 c->timing.n_launch++;
             }
+            // the fold-in list: every guest's row drawn from this sweep's V and the user half's
+            // hyperparameters (the host's values: this sweep's, whatever d_hyper holds by now),
+            // then, on a collected sweep, the guests' scores of this sample
+            if (c->fn) {
+                const size_t Kp = c->Kp;
+                double* h = c->h_fhyp;
+                HIPCHK(hipEventSynchronize(c->fev[0]));  // the previous copy out of the staging area
+                std::fill(h, h + 2 * Kp, 0.0);
+                std::copy(c->sig_u.begin(), c->sig_u.begin() + K, h);
+                std::copy(c->mu_u.begin(), c->mu_u.begin() + K, h + Kp);
+                HIPCHK(hipMemcpyAsync(c->d_fhyp.p, h, 2 * Kp * sizeof(double), hipMemcpyHostToDevice, se));
+                HIPCHK(hipEventRecord(c->fev[0], se));
+                HIPCHK(launch_foldin<T>(c->fn, c->d_forder.as<uint32_t>(), c->d_fptr.as<uint32_t>(), c->d_fitems.as<uint32_t>(),
+                                        c->d_fratings.as<double>(), c->d_fG.as<T>(), c->d_V.as<T>(), K, c->Kp,
+                                        c->d_fhyp.as<double>(), c->tau, c->sd_is_var, cf.seed, c->sweep,
+                                        c->d_fE.as<double>(), se));
+                HIPCHK(hipEventRecord(c->fev[1], se));
+                c->fdrawn++;
+                c->ftimed_draw = true;
+                c->timing.n_launch++;
+                if (collect) {
+                    HIPCHK(launch_watch_accum<T>(c->d_fident.as<uint32_t>(), c->fn, c->d_fG.as<T>(), c->d_V.as<T>(), c->J,
+                                                 c->Kp, nullptr, nullptr, 0.0, c->fclamp, c->lo, c->hi,
+                                                 c->d_fS1.as<double>(), c->d_fS2.as<double>(), se));
+                    HIPCHK(hipEventRecord(c->fev[2], se));
+                    c->fcount++;
+                    c->ftimed_score = true;
+                    c->timing.n_launch++;
+                }
+            }
             HIPCHK(hipEventRecord(c->ev[6], se));
         };
         if (par_eval) {
@@ -1740,6 +1788,8 @@ sbmf_ctx::~sbmf_ctx() {
     for (hipEvent_t& e : cev) event_destroy(e);
     for (hipEvent_t& e : oev) event_destroy(e);
     for (hipEvent_t& e : wev) event_destroy(e);
+    for (hipEvent_t& e : fev) event_destroy(e);
+    pinned_free(h_fhyp, h_fhyp_bytes);
     event_destroy(hev);
     stream_destroy(sto);
     stream_destroy(sto2);
@@ -2391,6 +2441,208 @@ int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select) {
         }
     }
     if (ms_select) *ms_select = ctx->wtimed_select ? sbmf::ev_ms(ctx->wev[2], ctx->wev[3]) : 0.0;
+    API_END(ctx)
+}
+
+// --- fold-in list ----------------------------------------------------------------------------
+// What the fold-in list covers; everything else is SBMF_E_STATE.
+static void foldin_scope(const sbmf_ctx* c, const char* fn) {
+    if (c->cfg.method != SBMF_METHOD_MCMC)
+        sbmf::fail(SBMF_E_STATE, "%s: the fold-in list is offered by the SBPMF sampler (SBMF_METHOD_MCMC) only; this "
+                                 "context runs the %s learner", fn,
+                   c->cfg.method == SBMF_METHOD_VB ? "online VB" : c->cfg.method == SBMF_METHOD_ALS ? "ALS" : "libFM MCMC");
+    if (c->bias)
+        sbmf::fail(SBMF_E_STATE, "%s: the fold-in list covers the unbiased quirk sets (final, sbpmf2, none); a guest of "
+                                 "the biased sampler (bias2 / bias22) would need a bias draw of its own", fn);
+    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no fold-in list there", fn);
+    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
+        sbmf::fail(SBMF_E_STATE, "%s: the fold-in list runs on one rank; this context joined a communicator", fn);
+    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+}
+static void foldin_drop(sbmf_ctx* c) {
+    for (sbmf::DBuf* d : {&c->d_fptr, &c->d_fitems, &c->d_fratings, &c->d_fident, &c->d_forder, &c->d_fG, &c->d_fE, &c->d_fhyp,
+                          &c->d_fS1, &c->d_fS2})
+        d->release();
+    sbmf::pinned_free(c->h_fhyp, c->h_fhyp_bytes);
+    c->h_fhyp_bytes = 0;
+    for (hipEvent_t& e : c->fev) sbmf::event_destroy(e);
+    c->fn = c->fJp = c->fdrawn = c->fcount = 0;
+    c->fclamp = 0;
+    c->ftimed_draw = c->ftimed_score = c->ftimed_select = false;
+}
+// the list's queued work is done (it runs on the evaluation's stream, which the compute stream
+// waits for before the sweep's results are copied)
+static void foldin_sync(sbmf_ctx* c) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->sto));
+    HIPCHK(hipStreamSynchronize(c->st));
+}
+static void foldin_ready(sbmf_ctx* c, const char* fn, bool sums) {
+    if (!c->fn) sbmf::fail(SBMF_E_STATE, "%s: no fold-in list registered (sbmf_foldin_users)", fn);
+    if (!c->fdrawn) sbmf::fail(SBMF_E_STATE, "%s: no sweep drawn since the fold-in list was registered", fn);
+    if (sums && !c->fcount)
+        sbmf::fail(SBMF_E_STATE, "%s: no sweep accumulated since the fold-in list was registered (burn-in sweeps draw "
+                                 "the rows but are not collected)", fn);
+    foldin_sync(c);
+}
+
+int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                      uint32_t flags) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    foldin_scope(ctx, "sbmf_foldin_users");
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
+    if (n && !ptr) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null ptr with n > 0");
+    if (n >= 0xfffffffeu) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: %u guests are too many", n);
+    for (uint32_t g = 0; g < n; ++g)
+        if (ptr[g + 1] < ptr[g])
+            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: ptr decreases at guest %u (%u then %u)", g, ptr[g], ptr[g + 1]);
+    const uint32_t p0 = n ? ptr[0] : 0, nnz = n ? ptr[n] - p0 : 0;
+    if (nnz && (!items || !ratings)) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null items / ratings with ratings listed");
+    for (uint32_t q = 0; q < nnz; ++q)
+        if (items[p0 + q] >= ctx->J)
+            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: items[%u] = %u is not below the %u items", p0 + q, items[p0 + q],
+                       ctx->J);
+    foldin_sync(ctx);
+    foldin_drop(ctx);
+    if (n == 0) return SBMF_OK;
+    const uint32_t Jp = sbmf::watch_jp(ctx->J), Kp = ctx->Kp;
+    const size_t ts = sbmf::tsize(ctx);
+    const size_t b_sum = (size_t)n * Jp * sizeof(double), b_G = ((size_t)n + 2) * Kp * ts;
+    const size_t b_tot = 2 * b_sum + b_G + ((size_t)n + 1 + 2 * (size_t)n + nnz) * sizeof(uint32_t) +
+                         ((size_t)2 * nnz + 2 * Kp) * sizeof(double);
+    try {
+        std::vector<uint32_t> hp(n + 1), ident(n);
+        for (uint32_t g = 0; g <= n; ++g) hp[g] = ptr[g] - p0;  // the device CSR starts at 0
+        for (uint32_t g = 0; g < n; ++g) ident[g] = g;
+        // the launch ends with its longest row: those start first
+        std::vector<uint32_t> order(ident);
+        std::stable_sort(order.begin(), order.end(),
+                         [&](uint32_t a, uint32_t b) { return hp[a + 1] - hp[a] > hp[b + 1] - hp[b]; });
+        hipStream_t st = ctx->st;
+        ctx->d_fS1.alloc(b_sum);
+        ctx->d_fS2.alloc(b_sum);
+        ctx->d_fG.alloc(b_G);
+        ctx->d_fE.alloc((size_t)nnz * sizeof(double));
+        ctx->d_fhyp.alloc((size_t)2 * Kp * sizeof(double));
+        ctx->d_fptr.alloc(hp.size() * sizeof(uint32_t));
+        ctx->d_fident.alloc(ident.size() * sizeof(uint32_t));
+        ctx->d_forder.alloc(order.size() * sizeof(uint32_t));
+        ctx->d_fitems.alloc((size_t)nnz * sizeof(uint32_t));
+        ctx->d_fratings.alloc((size_t)nnz * sizeof(double));
+        sbmf::pinned_alloc((void**)&ctx->h_fhyp, (size_t)2 * Kp * sizeof(double));
+        ctx->h_fhyp_bytes = (size_t)2 * Kp * sizeof(double);
+        for (hipEvent_t& e : ctx->fev) sbmf::event_create(&e);
+        HIPCHK(hipMemsetAsync(ctx->d_fS1.p, 0, b_sum, st));
+        HIPCHK(hipMemsetAsync(ctx->d_fS2.p, 0, b_sum, st));
+        HIPCHK(hipMemsetAsync(ctx->d_fG.p, 0, b_G, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_fptr.p, hp.data(), hp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_fident.p, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_forder.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (nnz) {
+            HIPCHK(hipMemcpyAsync(ctx->d_fitems.p, items + p0, (size_t)nnz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->d_fratings.p, ratings + p0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        ctx->fn = n;
+        ctx->fJp = Jp;
+        ctx->fclamp = (int)(flags & 1u);
+    } catch (const sbmf::Error& e) {
+        foldin_drop(ctx);
+        if (e.code == SBMF_E_NOMEM)
+            sbmf::fail(SBMF_E_NOMEM, "sbmf_foldin_users: %u guests with %u ratings need %zu bytes of device memory: %s", n,
+                       nnz, b_tot, e.msg.c_str());
+        throw;
+    } catch (...) {
+        foldin_drop(ctx);
+        throw;
+    }
+    API_END(ctx)
+}
+
+int sbmf_foldin_factors(sbmf_ctx* ctx, double* rows) {
+    API_BEGIN
+    if (!ctx || !rows) sbmf::fail(SBMF_E_ARG, "null argument");
+    foldin_scope(ctx, "sbmf_foldin_factors");
+    foldin_ready(ctx, "sbmf_foldin_factors", false);
+    if (ctx->cfg.precision == SBMF_F32)
+        sbmf::download_table<float>(ctx, ctx->d_fG, rows, ctx->fn);
+    else
+        sbmf::download_table<double>(ctx, ctx->d_fG, rows, ctx->fn);
+    API_END(ctx)
+}
+
+int sbmf_foldin_scores(sbmf_ctx* ctx, uint32_t g, double* mean, double* stdev) {
+    API_BEGIN
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    foldin_scope(ctx, "sbmf_foldin_scores");
+    foldin_ready(ctx, "sbmf_foldin_scores", true);
+    if (g >= ctx->fn) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_scores: row %u of a fold-in list of %u", g, ctx->fn);
+    const uint32_t J = ctx->J;
+    sbmf::DBuf tmp;
+    tmp.alloc((size_t)2 * J * sizeof(double));
+    double* d = tmp.as<double>();
+    HIPCHK(sbmf::launch_watch_moments(ctx->d_fS1.as<double>() + (size_t)g * ctx->fJp,
+                                      ctx->d_fS2.as<double>() + (size_t)g * ctx->fJp, J, (double)ctx->fcount, d, d + J,
+                                      ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    API_END(ctx)
+}
+
+int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                          double* stdev) {
+    API_BEGIN
+    if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    foldin_scope(ctx, "sbmf_foldin_recommend");
+    if (topn < 1 || topn > 1024) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_recommend: topn %u is not in 1..1024", topn);
+    if (flags & ~1u)
+        sbmf::fail(SBMF_E_ARG, "sbmf_foldin_recommend: unknown flags 0x%x (bit 0 = keep rated items)", flags & ~1u);
+    if (!(risk == risk)) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_recommend: risk is NaN");
+    foldin_ready(ctx, "sbmf_foldin_recommend", true);
+    const uint32_t n = ctx->fn, J = ctx->J, Jw = sbmf::watch_jw(J);
+    const size_t slots = (size_t)n * topn;
+    sbmf::DBuf d_it, d_ms, d_mask;
+    d_it.alloc(slots * sizeof(uint32_t));
+    d_ms.alloc(2 * slots * sizeof(double));
+    const bool exclude = !(flags & 1u);
+    if (exclude) d_mask.alloc((size_t)n * Jw * sizeof(uint32_t));
+    hipStream_t st = ctx->st;
+    HIPCHK(hipEventRecord(ctx->fev[3], st));
+    if (exclude) {  // "rated": the guest's own items (the guest CSR in the user-side CSR's place)
+        HIPCHK(hipMemsetAsync(d_mask.p, 0, (size_t)n * Jw * sizeof(uint32_t), st));
+        HIPCHK(sbmf::launch_watch_mask(ctx->d_fident.as<uint32_t>(), n, ctx->d_fptr.as<uint32_t>(),
+                                       ctx->d_fitems.as<uint32_t>(), d_mask.as<uint32_t>(), Jw, st));
+    }
+    HIPCHK(sbmf::launch_watch_select(n, ctx->d_fS1.as<double>(), ctx->d_fS2.as<double>(), J, (double)ctx->fcount, risk,
+                                     exclude ? d_mask.as<uint32_t>() : nullptr, topn, d_it.as<uint32_t>(),
+                                     d_ms.as<double>(), d_ms.as<double>() + slots, st));
+    HIPCHK(hipEventRecord(ctx->fev[4], st));
+    HIPCHK(hipStreamSynchronize(st));
+    ctx->ftimed_select = true;
+    HIPCHK(hipMemcpy(items, d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mean, d_ms.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d_ms.as<double>() + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+    API_END(ctx)
+}
+
+int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    foldin_scope(ctx, "sbmf_foldin_timing");
+    if (!ctx->fn) sbmf::fail(SBMF_E_STATE, "sbmf_foldin_timing: no fold-in list registered (sbmf_foldin_users)");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if (ms_draw) *ms_draw = 0.0;
+    if (ms_score) *ms_score = 0.0;
+    if (ctx->ftimed_draw) {
+        foldin_sync(ctx);
+        if (ms_draw) *ms_draw = sbmf::ev_ms(ctx->fev[0], ctx->fev[1]);
+        // (collected sweeps follow the burn-in: once a scoring launch was timed, the last
+        // sweep's draw end is its begin)
+        if (ms_score && ctx->ftimed_score) *ms_score = sbmf::ev_ms(ctx->fev[1], ctx->fev[2]);
+    }
+    if (ms_select) *ms_select = ctx->ftimed_select ? sbmf::ev_ms(ctx->fev[3], ctx->fev[4]) : 0.0;
     API_END(ctx)
 }
 

@@ -11,7 +11,9 @@
 // running-mean test RMSE per line, :57-62,146); -out writes one averaged
 // prediction per test line (libfm.cpp:629-634).
 // Beyond libFM: -recommend / -rec_users / -rec_topn / -rec_risk write the SBPMF sampler's
-// posterior top-N items for a list of users (sbmf_watch_users / sbmf_recommend).
+// posterior top-N items for a list of users (sbmf_watch_users / sbmf_recommend);
+// -rec_guests / -recommend_guests do the same for users outside the training set, given by
+// their ratings (sbmf_foldin_users / sbmf_foldin_recommend).
 // Differences, by design: -seed is honoured (libfm.cpp:124 ignores it); on
 // error the exit code is 1 (the reference prints "ERROR" and returns 0).
 #include <algorithm>
@@ -389,6 +391,13 @@ int main(int argc, char** argv) {
         cl.reg("rec_users", "filename with one user id per line [MANDATORY with -recommend]");
         cl.reg("rec_topn", "items per user, 1..1024; default=10");
         cl.reg("rec_risk", "rank by mean - x * stdev (a lower confidence bound for x > 0); default=0");
+        // the same for guests: users outside the training set (sbmf_foldin_users / sbmf_foldin_recommend)
+        cl.reg("rec_guests", "filename with one 'guest item rating' line per rating of a user outside the training "
+                             "set: guests numbered from 0, the numbers non-decreasing (a skipped number is a guest "
+                             "without ratings), item ids as -recommend prints them [MANDATORY with -recommend_guests]");
+        cl.reg("recommend_guests", "filename for output: -recommend's lines for the guests of -rec_guests ('guest<TAB>"
+                                   "item<TAB>mean<TAB>stdev', the guest's own items left out); shares -rec_topn and "
+                                   "-rec_risk; the SBPMF sampler with the unbiased quirk sets only");
         if (cl.has("help") || argc == 1) {
             cl.print_help();
             return leave(0);
@@ -403,11 +412,20 @@ int main(int argc, char** argv) {
         if (rec && cl.get("recommend", "").empty()) throw std::runtime_error("-recommend needs a file name");
         if (rec && cl.get("rec_users", "").empty())
             throw std::runtime_error("-recommend needs -rec_users <file> (one user id per line)");
-        if (!rec && (cl.has("rec_users") || cl.has("rec_topn") || cl.has("rec_risk")))
+        const bool recg = cl.has("recommend_guests");
+        const char* recg_refusal = "-recommend_guests is offered by the SBPMF sampler (-method mcmc -order sbpmf) with "
+                                   "the unbiased quirk sets (final, sbpmf2, none)";
+        if (recg && cl.get("recommend_guests", "").empty()) throw std::runtime_error("-recommend_guests needs a file name");
+        if (recg && cl.get("rec_guests", "").empty())
+            throw std::runtime_error("-recommend_guests needs -rec_guests <file> ('guest item rating' per line)");
+        if (!recg && cl.has("rec_guests")) throw std::runtime_error("-rec_guests goes with -recommend_guests <file>");
+        if (!rec && cl.has("rec_users")) throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
+        if (!rec && !recg && (cl.has("rec_topn") || cl.has("rec_risk")))
             throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
         if (rec && method != "mcmc") throw std::runtime_error(rec_refusal);  // before any file is opened
+        if (recg && method != "mcmc") throw std::runtime_error(recg_refusal);
         const long rec_topn = cl.getl("rec_topn", 10);
-        if (rec && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
+        if ((rec || recg) && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
         const std::string fmt = cl.get("format", "auto");
         if (fmt != "auto" && fmt != "triple" && fmt != "libfm" && fmt != "binary")
             throw std::runtime_error("unknown -format " + fmt);
@@ -427,6 +445,7 @@ int main(int argc, char** argv) {
         // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
         const bool lfm = als || (method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
         if (rec && lfm) throw std::runtime_error(rec_refusal);
+        if (recg && (lfm || biased)) throw std::runtime_error(recg_refusal);  // (a guest bias would need its own draw)
         if (method != "mcmc" && !vb && !als)
             throw std::runtime_error("-method " + method + " is not supported (use mcmc, als or vb)");
         if (!cl.has("train") || !cl.has("test")) throw std::runtime_error("-train and -test are mandatory");
@@ -511,7 +530,7 @@ int main(int argc, char** argv) {
         // With one user and one item feature per line that is the users-first layout with
         // item offset num_user, so no flag is needed (-item_offset overrides it).
         // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
-        if ((lfm || vb || rec) && libfm_input && !cl.has("item_offset")) off = users_first_offset(tr, te);
+        if ((lfm || vb || rec || recg) && libfm_input && !cl.has("item_offset")) off = users_first_offset(tr, te);
         std::vector<uint32_t> rec_ids;
         if (rec) {
             std::ifstream f(cl.get("rec_users", ""));
@@ -527,6 +546,34 @@ int main(int argc, char** argv) {
                 rec_ids.push_back((uint32_t)v);
             }
             if (rec_ids.empty()) throw std::runtime_error("-rec_users: " + cl.get("rec_users", "") + " lists no user");
+        }
+        // the guests' CSR; item ids come in the id space -recommend prints (on libFM input the feature id)
+        std::vector<uint32_t> g_ptr, g_items;
+        std::vector<double> g_ratings;
+        if (recg) {
+            const std::string gf = cl.get("rec_guests", "");
+            std::ifstream f(gf);
+            if (!f.is_open()) throw std::runtime_error("Unable to open file " + gf);
+            const unsigned long long ioff = libfm_input ? off : 0;
+            std::string line;
+            g_ptr.push_back(0);
+            while (std::getline(f, line)) {
+                const size_t p = line.find_first_not_of(" \t\r");
+                if (p == std::string::npos || line[p] == '#') continue;
+                unsigned long long g = 0, it = 0;
+                double r = 0.0;
+                if (std::sscanf(line.c_str() + p, "%llu %llu %lf", &g, &it, &r) != 3 || g > 0xfffffffdull)
+                    throw std::runtime_error("-rec_guests: cannot read 'guest item rating' from '" + line + "'");
+                if (g + 2 < g_ptr.size())  // the open guest is number g_ptr.size() - 2
+                    throw std::runtime_error("-rec_guests: guest numbers must not decrease ('" + line + "')");
+                if (it < ioff || it - ioff > 0xfffffffeull)
+                    throw std::runtime_error("-rec_guests: item id out of range in '" + line + "'");
+                while (g_ptr.size() < g + 2) g_ptr.push_back((uint32_t)g_items.size());  // opens guest g (and skipped ones)
+                g_items.push_back((uint32_t)(it - ioff));
+                g_ratings.push_back(r);
+                g_ptr.back() = (uint32_t)g_items.size();
+            }
+            if (g_ptr.size() < 2) throw std::runtime_error("-rec_guests: " + gf + " lists no guest");
         }
 
         sbmf_ctx* ctx = nullptr;
@@ -577,6 +624,8 @@ int main(int argc, char** argv) {
         }
         rs.verbosity = (int)cl.getl("verbosity", 0);
         if (rec) chk(sbmf_watch_users(ctx, (uint32_t)rec_ids.size(), rec_ids.data(), 0));
+        if (recg)
+            chk(sbmf_foldin_users(ctx, (uint32_t)g_ptr.size() - 1, g_ptr.data(), g_items.data(), g_ratings.data(), 0));
         chk(sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
         if (rec) {
             const size_t topn = (size_t)rec_topn, slots = rec_ids.size() * topn;
@@ -593,6 +642,22 @@ int main(int argc, char** argv) {
                     if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
                     std::fprintf(f, "%u\t%llu\t%.17g\t%.17g\n", rec_ids[w], (unsigned long long)(it[x] + ioff), mean[x],
                                  sd[x]);
+                }
+            std::fclose(f);
+        }
+        if (recg) {
+            const size_t ng = g_ptr.size() - 1, topn = (size_t)rec_topn, slots = ng * topn;
+            std::vector<uint32_t> it(slots);
+            std::vector<double> mean(slots), sd(slots);
+            chk(sbmf_foldin_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
+            FILE* f = std::fopen(cl.get("recommend_guests", "").c_str(), "w");
+            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend_guests", ""));
+            const uint64_t ioff = libfm_input ? off : 0;
+            for (size_t g = 0; g < ng; ++g)
+                for (size_t k = 0; k < topn; ++k) {
+                    const size_t x = g * topn + k;
+                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
+                    std::fprintf(f, "%zu\t%llu\t%.17g\t%.17g\n", g, (unsigned long long)(it[x] + ioff), mean[x], sd[x]);
                 }
             std::fclose(f);
         }

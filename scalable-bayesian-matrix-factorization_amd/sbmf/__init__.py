@@ -386,6 +386,63 @@ class FMLearnSBPMF:
         self._check(lib.sbmf_watch_timing(self.ctx, C.byref(a), C.byref(b)))
         return {"ms_score": a.value, "ms_select": b.value}
 
+    # -- posterior top-N for guests: users outside the training set, given by their ratings
+    def foldin(self, guests, clamp=False):
+        """Register a fold-in list (sbmf_foldin_users): ``guests`` is a list of
+        (items, ratings) pairs, one per guest (both may be empty), or a CSR as a tuple
+        (ptr, items, ratings) of three 1-D numpy arrays.  From the next sweep on every guest's
+        factor row is drawn beside the chain and its scores accumulated on collected
+        sweeps.  An empty list drops the fold-in list and frees its device buffers."""
+        if isinstance(guests, tuple) and len(guests) == 3 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in guests):
+            ptr, items, ratings = _u32(guests[0]), _u32(guests[1]), _f64(guests[2])
+        else:
+            ptr = np.zeros(len(guests) + 1, dtype=np.int64)
+            for g, (it, _) in enumerate(guests):
+                ptr[g + 1] = ptr[g] + len(it)
+            ptr = _u32(ptr)
+            items = _u32(np.concatenate([np.asarray(it, dtype=np.int64).ravel() for it, _ in guests] + [np.zeros(0, np.int64)]))
+            ratings = _f64(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for _, r in guests] + [np.zeros(0)]))
+            if len(items) != len(ratings):
+                raise ValueError("a guest's items and ratings differ in length")
+        n = max(len(ptr) - 1, 0)
+        if n == 0:
+            ptr = np.zeros(1, np.uint32)
+        self._check(lib.sbmf_foldin_users(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                                          _ptr(ratings, C.c_double), 1 if clamp else 0))
+        self._n_guests = n
+
+    def foldin_factors(self):
+        """The current sample's guest rows [n, K] (the last sweep's draw)."""
+        rows = np.zeros((max(getattr(self, "_n_guests", 0), 1), self.cfg.num_factor))
+        self._check(lib.sbmf_foldin_factors(self.ctx, _ptr(rows, C.c_double)))
+        return rows[:getattr(self, "_n_guests", 0)]
+
+    def foldin_scores(self, g):
+        """(mean, stdev) of guest ``g`` over the sweeps collected since ``foldin``, one value per item."""
+        _, ni, _, _ = self.dims()
+        mean, sd = np.zeros(ni), np.zeros(ni)
+        self._check(lib.sbmf_foldin_scores(self.ctx, int(g), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        return mean, sd
+
+    def foldin_recommend(self, topn=10, exclude_rated=True, risk=0.0):
+        """``recommend`` for the guests; "rated" means the guest's own items."""
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        n, t = getattr(self, "_n_guests", 0), int(topn)
+        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
+        self._check(lib.sbmf_foldin_recommend(self.ctx, t, 0 if exclude_rated else 1, float(risk),
+                                              _ptr(items, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = items[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def foldin_timing(self):
+        """Device ms of the last sweep's draw and scoring launch and of the last selection."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(lib.sbmf_foldin_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"ms_draw": a.value, "ms_score": b.value, "ms_select": c.value}
+
     def close(self):
         if self.ctx is not None:
             lib.sbmf_destroy(self.ctx)

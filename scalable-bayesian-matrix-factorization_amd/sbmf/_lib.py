@@ -106,6 +106,11 @@ SIGNATURES = {
     "sbmf_watch_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
     "sbmf_recommend": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
     "sbmf_watch_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64]),
+    "sbmf_foldin_users": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_U32, _P_F64, C.c_uint32]),
+    "sbmf_foldin_factors": (C.c_int, [C.c_void_p, _P_F64]),
+    "sbmf_foldin_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_foldin_recommend": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
+    "sbmf_foldin_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
     "sbmf_comm_unique_id": (C.c_int, [_P_U8]),
     "sbmf_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P_U8]),
     "sbmf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P_U8, C.POINTER(C.c_void_p)]),
