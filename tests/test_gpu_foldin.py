@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 from conftest import write_m1m100k_libfm
+from edge_rows import restate_row as restate  # the header's coordinate loop for one row in a floating type
 from sbmf import (SBMF_E_ARG, SBMF_E_STATE, Data, FMLearnSBPMF, SBMFError, device_usage, philox_normals)
 from sbmf._lib import CLI_PATH, lib
 
@@ -56,25 +57,6 @@ def make_guests(tr, lengths, seed=5, repeats=True):
         items = np.concatenate([rng.permutation(J), rng.permutation(J)[:18]]).astype(np.uint32)
         out.append((items, rng.choice(tr[2], len(items))))
     return out
-
-
-def restate(V, sig, mu, tau, u, z, items, r, sd_is_var, dt):
-    """The header's coordinate loop for one guest in the floating type dt."""
-    K = len(u)
-    Vg = V[items.astype(np.int64)].astype(dt)
-    u = u.astype(dt).copy()
-    sig, mu, z, tau = sig.astype(dt), mu.astype(dt), z.astype(dt), dt(tau)
-    e = r.astype(dt) - Vg @ u
-    for k in range(K):
-        v = Vg[:, k]
-        P = (v * v).sum(dtype=dt)
-        Q = (v * (e + v * u[k])).sum(dtype=dt)
-        var = dt(1) / (sig[k] + tau * P)
-        mean = var * (tau * Q + sig[k] * mu[k])
-        un = mean + (var if sd_is_var else np.sqrt(var)) * z[k]
-        e = e + v * (u[k] - un)
-        u[k] = un
-    return u
 
 
 def step_draw(L, guests, prev, sweep, seed, K, sd_is_var, f32, what):
