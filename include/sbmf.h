@@ -180,10 +180,13 @@ typedef struct sbmf_config {
                                  sweep s+1's start (its hyperparameter upload and user half) is
                                  queued before sweep s is reported to the run callback, so the
                                  device does not idle through the host's per-sweep work.  The
-                                 chain and the reports are the same; the callback must not read
-                                 device state (factors, predictions), and a stop it asks for takes
-                                 effect after sweep s+1.  0 (default): each sweep is reported with
-                                 the device idle after it                                         */
+                                 chain and the reports are the same.  In sweep s's callback
+                                 sbmf_predict and the hyperparameter getters (sbmf_get_hyper,
+                                 sbmf_get_biases' b0) are valid and describe sweep s; the factors
+                                 (sbmf_get_factors) are not, because sweep s+1's user half may be
+                                 running.  A stop the callback asks for takes effect after sweep
+                                 s+1.  0 (default): each sweep is reported with the device idle
+                                 after it                                                         */
 } sbmf_config;
 
 /* Per-sweep report passed to the run callback. */

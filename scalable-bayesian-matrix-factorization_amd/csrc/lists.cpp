@@ -1,0 +1,316 @@
+// lists.cpp -- the score lists (ScoreList, ctx.h) and their entry points: the watch list
+// (sbmf_watch_*, sbmf_recommend) and the fold-in list (sbmf_foldin_*).
+#include "ctx.h"
+
+void ScoreList::alloc(uint32_t n_, uint32_t J, int clamp_, hipStream_t st) {
+    n = n_;
+    Jp = sbmf::watch_jp(J);
+    clamp = clamp_;
+    const size_t bytes = (size_t)n * Jp * sizeof(double);
+    d_S1.alloc(bytes);
+    d_S2.alloc(bytes);
+    d_ids.alloc((size_t)n * sizeof(uint32_t));
+    for (hipEvent_t& e : sel) sbmf::event_create(&e);
+    HIPCHK(hipMemsetAsync(d_S1.p, 0, bytes, st));
+    HIPCHK(hipMemsetAsync(d_S2.p, 0, bytes, st));
+}
+void ScoreList::drop() {
+    for (sbmf::DBuf* d : {&d_ids, &d_S1, &d_S2}) d->release();
+    for (hipEvent_t& e : sel) sbmf::event_destroy(e);
+    n = Jp = count = 0;
+    clamp = 0;
+    timed_select = false;
+}
+// this sample's scores of the list's rows of `rows` (a factor table: U, or the guests' G) against
+// every item, added to the sums; the caller records the events around it
+template <typename T>
+void ScoreList::accumulate(sbmf_ctx* c, const T* rows, const double* bu, const double* bv, double b0, hipStream_t se) {
+    HIPCHK(sbmf::launch_watch_accum<T>(d_ids.as<uint32_t>(), n, rows, c->d_V.as<T>(), c->J, c->Kp, bu, bv, b0, clamp,
+                                       c->lo, c->hi, d_S1.as<double>(), d_S2.as<double>(), se));
+    count++;
+    c->launches++;
+}
+template void ScoreList::accumulate<float>(sbmf_ctx*, const float*, const double*, const double*, double, hipStream_t);
+template void ScoreList::accumulate<double>(sbmf_ctx*, const double*, const double*, const double*, double, hipStream_t);
+void ScoreList::scores(sbmf_ctx* c, const char* fn, uint32_t row, double* mean, double* stdev) {
+    if (row >= n) sbmf::fail(SBMF_E_ARG, "%s: row %u of a %s of %u", fn, row, what, n);
+    const uint32_t J = c->J;
+    sbmf::DBuf tmp;
+    tmp.alloc((size_t)2 * J * sizeof(double));
+    double* d = tmp.as<double>();
+    HIPCHK(sbmf::launch_watch_moments(d_S1.as<double>() + (size_t)row * Jp, d_S2.as<double>() + (size_t)row * Jp, J,
+                                      (double)count, d, d + J, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+}
+// top-N of every row; "rated" items (flags bit 0 clear: left out) are those of the rows' CSR --
+// the user side's for watched users, the guest CSR for guests
+void ScoreList::recommend(sbmf_ctx* c, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn,
+                          uint32_t flags, double risk, uint32_t* items, double* mean, double* stdev) {
+    const uint32_t J = c->J, Jw = sbmf::watch_jw(J);
+    const size_t slots = (size_t)n * topn;
+    sbmf::DBuf d_it, d_ms, d_mask;
+    d_it.alloc(slots * sizeof(uint32_t));
+    d_ms.alloc(2 * slots * sizeof(double));
+    const bool exclude = !(flags & 1u);
+    if (exclude) d_mask.alloc((size_t)n * Jw * sizeof(uint32_t));
+    hipStream_t st = c->st;
+    HIPCHK(hipEventRecord(sel[0], st));
+    if (exclude) {
+        HIPCHK(hipMemsetAsync(d_mask.p, 0, (size_t)n * Jw * sizeof(uint32_t), st));
+        HIPCHK(sbmf::launch_watch_mask(d_ids.as<uint32_t>(), n, csr_ptr, csr_items, d_mask.as<uint32_t>(), Jw, st));
+    }
+    HIPCHK(sbmf::launch_watch_select(n, d_S1.as<double>(), d_S2.as<double>(), J, (double)count, risk,
+                                     exclude ? d_mask.as<uint32_t>() : nullptr, topn, d_it.as<uint32_t>(),
+                                     d_ms.as<double>(), d_ms.as<double>() + slots, st));
+    HIPCHK(hipEventRecord(sel[1], st));
+    HIPCHK(hipStreamSynchronize(st));
+    timed_select = true;
+    HIPCHK(hipMemcpy(items, d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mean, d_ms.p, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d_ms.as<double>() + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+extern "C" {
+
+// The learners and schedules a list covers; everything else is SBMF_E_STATE.
+static void list_scope(const sbmf_ctx* c, const ScoreList& l, const char* fn, bool unbiased_only) {
+    if (c->cfg.method != SBMF_METHOD_MCMC)
+        sbmf::fail(SBMF_E_STATE, "%s: the %s is offered by the SBPMF sampler (SBMF_METHOD_MCMC) only; this "
+                                 "context runs the %s learner", fn, l.what,
+                   c->cfg.method == SBMF_METHOD_VB ? "online VB" : c->cfg.method == SBMF_METHOD_ALS ? "ALS" : "libFM MCMC");
+    if (unbiased_only && c->bias)
+        sbmf::fail(SBMF_E_STATE, "%s: the %s covers the unbiased quirk sets (final, sbpmf2, none); a guest of "
+                                 "the biased sampler (bias2 / bias22) would need a bias draw of its own", fn, l.what);
+    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no %s there", fn, l.what);
+    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
+        sbmf::fail(SBMF_E_STATE, "%s: the %s runs on one rank; this context joined a communicator", fn, l.what);
+    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+}
+// a list's queued work is done (it runs on the evaluation's stream, which the compute stream
+// waits for before the sweep's results are copied)
+static void list_sync(sbmf_ctx* c) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->sto));
+    HIPCHK(hipStreamSynchronize(c->st));
+}
+static void list_registered(const ScoreList& l, const char* fn) {
+    if (!l.n) sbmf::fail(SBMF_E_STATE, "%s: no %s registered (%s)", fn, l.what, l.reg);
+}
+// registered, and (sums) at least one sweep accumulated; `note`: what else the caller has to say
+// about a list with none
+static void list_ready(sbmf_ctx* c, const ScoreList& l, const char* fn, bool sums = true, const char* note = "") {
+    list_registered(l, fn);
+    if (sums && !l.count)
+        sbmf::fail(SBMF_E_STATE, "%s: no sweep accumulated since the %s was registered%s", fn, l.what, note);
+    list_sync(c);
+}
+// the arguments sbmf_recommend and sbmf_foldin_recommend share
+static void recommend_args(const char* fn, uint32_t topn, uint32_t flags, double risk) {
+    if (topn < 1 || topn > 1024) sbmf::fail(SBMF_E_ARG, "%s: topn %u is not in 1..1024", fn, topn);
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "%s: unknown flags 0x%x (bit 0 = keep rated items)", fn, flags & ~1u);
+    if (!(risk == risk)) sbmf::fail(SBMF_E_ARG, "%s: risk is NaN", fn);
+}
+
+static void watch_drop(sbmf_ctx* c) {
+    c->watch.drop();
+    for (hipEvent_t& e : c->wev) sbmf::event_destroy(e);
+}
+
+int sbmf_watch_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t flags) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    list_scope(ctx, ctx->watch, "sbmf_watch_users", false);
+    if (n && !users) sbmf::fail(SBMF_E_ARG, "null user list with n > 0");
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_watch_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
+    for (uint32_t w = 0; w < n; ++w)
+        if (users[w] >= ctx->I)
+            sbmf::fail(SBMF_E_ARG, "sbmf_watch_users: users[%u] = %u is not below the %u users", w, users[w], ctx->I);
+    list_sync(ctx);
+    watch_drop(ctx);
+    if (n == 0) return SBMF_OK;
+    try {
+        ctx->watch.alloc(n, ctx->J, (int)(flags & 1u), ctx->st);
+        for (hipEvent_t& e : ctx->wev) sbmf::event_create(&e);
+        HIPCHK(hipMemcpyAsync(ctx->watch.d_ids.p, users, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->st));
+        HIPCHK(hipStreamSynchronize(ctx->st));
+    } catch (...) {
+        watch_drop(ctx);
+        throw;
+    }
+    API_END(ctx)
+}
+
+int sbmf_watch_scores(sbmf_ctx* ctx, uint32_t w, double* mean, double* stdev) {
+    API_BEGIN
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    list_scope(ctx, ctx->watch, "sbmf_watch_scores", false);
+    list_ready(ctx, ctx->watch, "sbmf_watch_scores");
+    ctx->watch.scores(ctx, "sbmf_watch_scores", w, mean, stdev);
+    API_END(ctx)
+}
+
+int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                   double* stdev) {
+    API_BEGIN
+    if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    list_scope(ctx, ctx->watch, "sbmf_recommend", false);
+    recommend_args("sbmf_recommend", topn, flags, risk);
+    list_ready(ctx, ctx->watch, "sbmf_recommend");
+    ctx->watch.recommend(ctx, ctx->d_uptr.as<uint32_t>(), ctx->d_upart.as<uint32_t>(), topn, flags, risk, items, mean,
+                         stdev);
+    API_END(ctx)
+}
+
+int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    list_scope(ctx, ctx->watch, "sbmf_watch_timing", false);
+    list_registered(ctx->watch, "sbmf_watch_timing");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if (ms_score) {
+        *ms_score = 0.0;
+        if (ctx->watch.count) {
+            HIPCHK(hipEventSynchronize(ctx->wev[1]));
+            *ms_score = sbmf::ev_ms(ctx->wev[0], ctx->wev[1]);
+        }
+    }
+    if (ms_select) *ms_select = ctx->watch.timed_select ? sbmf::ev_ms(ctx->watch.sel[0], ctx->watch.sel[1]) : 0.0;
+    API_END(ctx)
+}
+
+// --- fold-in list ----------------------------------------------------------------------------
+static void foldin_drop(sbmf_ctx* c) {
+    c->guests.drop();
+    for (sbmf::DBuf* d : {&c->d_fptr, &c->d_fitems, &c->d_fratings, &c->d_forder, &c->d_fG, &c->d_fE, &c->d_fhyp})
+        d->release();
+    sbmf::pinned_free(c->h_fhyp, c->h_fhyp_bytes);
+    c->h_fhyp_bytes = 0;
+    for (hipEvent_t& e : c->fev) sbmf::event_destroy(e);
+    c->fdrawn = 0;
+}
+static void foldin_ready(sbmf_ctx* c, const char* fn, bool sums) {
+    if (c->guests.n && !c->fdrawn)
+        sbmf::fail(SBMF_E_STATE, "%s: no sweep drawn since the fold-in list was registered", fn);
+    list_ready(c, c->guests, fn, sums, " (burn-in sweeps draw the rows but are not collected)");
+}
+
+int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                      uint32_t flags) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    list_scope(ctx, ctx->guests, "sbmf_foldin_users", true);
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
+    if (n && !ptr) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null ptr with n > 0");
+    if (n >= 0xfffffffeu) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: %u guests are too many", n);
+    for (uint32_t g = 0; g < n; ++g)
+        if (ptr[g + 1] < ptr[g])
+            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: ptr decreases at guest %u (%u then %u)", g, ptr[g], ptr[g + 1]);
+    const uint32_t p0 = n ? ptr[0] : 0, nnz = n ? ptr[n] - p0 : 0;
+    if (nnz && (!items || !ratings)) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null items / ratings with ratings listed");
+    for (uint32_t q = 0; q < nnz; ++q)
+        if (items[p0 + q] >= ctx->J)
+            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: items[%u] = %u is not below the %u items", p0 + q, items[p0 + q],
+                       ctx->J);
+    list_sync(ctx);
+    foldin_drop(ctx);
+    if (n == 0) return SBMF_OK;
+    const uint32_t Jp = sbmf::watch_jp(ctx->J), Kp = ctx->Kp;
+    const size_t ts = sbmf::tsize(ctx);
+    const size_t b_sum = (size_t)n * Jp * sizeof(double), b_G = ((size_t)n + 2) * Kp * ts;
+    const size_t b_tot = 2 * b_sum + b_G + ((size_t)n + 1 + 2 * (size_t)n + nnz) * sizeof(uint32_t) +
+                         ((size_t)2 * nnz + 2 * Kp) * sizeof(double);
+    try {
+        std::vector<uint32_t> hp(n + 1), ident(n);
+        for (uint32_t g = 0; g <= n; ++g) hp[g] = ptr[g] - p0;  // the device CSR starts at 0
+        for (uint32_t g = 0; g < n; ++g) ident[g] = g;
+        // the launch ends with its longest row: those start first
+        std::vector<uint32_t> order(ident);
+        std::stable_sort(order.begin(), order.end(),
+                         [&](uint32_t a, uint32_t b) { return hp[a + 1] - hp[a] > hp[b + 1] - hp[b]; });
+        hipStream_t st = ctx->st;
+        ctx->guests.alloc(n, ctx->J, (int)(flags & 1u), st);
+        ctx->d_fG.alloc(b_G);
+        ctx->d_fE.alloc((size_t)nnz * sizeof(double));
+        ctx->d_fhyp.alloc((size_t)2 * Kp * sizeof(double));
+        ctx->d_fptr.alloc(hp.size() * sizeof(uint32_t));
+        ctx->d_forder.alloc(order.size() * sizeof(uint32_t));
+        ctx->d_fitems.alloc((size_t)nnz * sizeof(uint32_t));
+        ctx->d_fratings.alloc((size_t)nnz * sizeof(double));
+        sbmf::pinned_alloc((void**)&ctx->h_fhyp, (size_t)2 * Kp * sizeof(double));
+        ctx->h_fhyp_bytes = (size_t)2 * Kp * sizeof(double);
+        for (hipEvent_t& e : ctx->fev) sbmf::event_create(&e);
+        HIPCHK(hipMemsetAsync(ctx->d_fG.p, 0, b_G, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_fptr.p, hp.data(), hp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->guests.d_ids.p, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_forder.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (nnz) {
+            HIPCHK(hipMemcpyAsync(ctx->d_fitems.p, items + p0, (size_t)nnz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->d_fratings.p, ratings + p0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    } catch (const sbmf::Error& e) {
+        foldin_drop(ctx);
+        if (e.code == SBMF_E_NOMEM)
+            sbmf::fail(SBMF_E_NOMEM, "sbmf_foldin_users: %u guests with %u ratings need %zu bytes of device memory: %s", n,
+                       nnz, b_tot, e.msg.c_str());
+        throw;
+    } catch (...) {
+        foldin_drop(ctx);
+        throw;
+    }
+    API_END(ctx)
+}
+
+int sbmf_foldin_factors(sbmf_ctx* ctx, double* rows) {
+    API_BEGIN
+    if (!ctx || !rows) sbmf::fail(SBMF_E_ARG, "null argument");
+    list_scope(ctx, ctx->guests, "sbmf_foldin_factors", true);
+    foldin_ready(ctx, "sbmf_foldin_factors", false);
+    sbmf::download_table(ctx, ctx->d_fG, rows, ctx->guests.n);
+    API_END(ctx)
+}
+
+int sbmf_foldin_scores(sbmf_ctx* ctx, uint32_t g, double* mean, double* stdev) {
+    API_BEGIN
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    list_scope(ctx, ctx->guests, "sbmf_foldin_scores", true);
+    foldin_ready(ctx, "sbmf_foldin_scores", true);
+    ctx->guests.scores(ctx, "sbmf_foldin_scores", g, mean, stdev);
+    API_END(ctx)
+}
+
+int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* items, double* mean,
+                          double* stdev) {
+    API_BEGIN
+    if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    list_scope(ctx, ctx->guests, "sbmf_foldin_recommend", true);
+    recommend_args("sbmf_foldin_recommend", topn, flags, risk);
+    foldin_ready(ctx, "sbmf_foldin_recommend", true);
+    // "rated": the guest's own items (the guest CSR in the user-side CSR's place)
+    ctx->guests.recommend(ctx, ctx->d_fptr.as<uint32_t>(), ctx->d_fitems.as<uint32_t>(), topn, flags, risk, items, mean,
+                          stdev);
+    API_END(ctx)
+}
+
+int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    list_scope(ctx, ctx->guests, "sbmf_foldin_timing", true);
+    list_registered(ctx->guests, "sbmf_foldin_timing");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if (ms_draw) *ms_draw = 0.0;
+    if (ms_score) *ms_score = 0.0;
+    if (ctx->fdrawn) {
+        list_sync(ctx);
+        if (ms_draw) *ms_draw = sbmf::ev_ms(ctx->fev[0], ctx->fev[1]);
+        // (collected sweeps follow the burn-in: once a scoring launch was timed, the last
+        // sweep's draw end is its begin)
+        if (ms_score && ctx->guests.count) *ms_score = sbmf::ev_ms(ctx->fev[1], ctx->fev[2]);
+    }
+    if (ms_select) *ms_select = ctx->guests.timed_select ? sbmf::ev_ms(ctx->guests.sel[0], ctx->guests.sel[1]) : 0.0;
+    API_END(ctx)
+}
+
+}  // extern "C"

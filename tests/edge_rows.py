@@ -13,11 +13,11 @@ library's own new U, so every row is an independent check of one kernel invocati
 Which kernel a row length runs on at default settings (the table the binning assertion keeps
 honest: expected_kinds() restates it, assert_binning() compares it with timing().kern_rows and
 fails with "edge list stale" when a threshold moves).  Lines of csrc/ that decide each edge:
-bins gk_maxdeg (kernels.h:46-52) through build_bins (sbmf.cpp:229-247) and the stream threshold
-(sbmf.cpp:503-504); kernel of a bin run_half (sbmf.cpp:1159-1173; k_grow's capacity grow_maxdeg,
-kernels.hip:1951; its KL form kernels.hip:1948); streaming set of a row sbmf.cpp:569; task size
-gstream_cmax (kernels.hip:1961, sbmf.cpp:575-576); chunks of a row build_stream_tasks
-(sbmf.cpp:823, 830).
+bins gk_maxdeg (kernels.h:46-52) through build_bins (prepare.cpp:133-151) and the stream threshold
+(prepare.cpp:196-197); kernel of a bin run_half (sweep.cpp:319-333; k_grow's capacity grow_maxdeg,
+kernels.hip:1951; its KL form kernels.hip:1948); streaming set of a row prepare.cpp:262; task size
+gstream_cmax (kernels.hip:1961, prepare.cpp:268-269); chunks of a row build_stream_tasks
+(prepare.cpp:515, 522).
 
   f64, users and items alike up to 256 ratings            kern_rows kind
     0..8        k_gblock, one quarter-wave row (GK_W4)        0 gblock_w4

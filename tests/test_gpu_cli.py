@@ -121,6 +121,8 @@ def test_cli_philox_bench_mode_matches_oracle(tmp_path, ml100k):
          "--recompute_every", "0", "-rlog", str(tmp_path / "rlog.tsv"))
     o = oracle.run(*ml100k, K=32, iters=20, seed=2015, rng="philox", want_factors=False)
     assert np.abs(_rlog(tmp_path / "rlog.tsv") - o["rmse"]).max() < 1e-6
+    # the CLI runs pipelined: the hyperparameter columns are still the reported sweep's
+    assert _close6(_rlog(tmp_path / "rlog.tsv", "alpha"), _rlog(tmp_path / "rlog.tsv", "sbmf_tau"))
 
 
 def _write_libfm(path, data, item_offset):

@@ -172,11 +172,28 @@ def test_evaluation_order_changes_nothing(ml100k):
 def test_pipelined_sweeps_change_nothing(ml100k, quirks):
     """sbmf_config.pipeline: sweep s+1's start (hyperparameter upload, user half) is queued
     before sweep s is reported.  The chain, every per-sweep report and the factors are the
-    same bit for bit; a stop asked for at sweep s takes effect after sweep s+1."""
+    same bit for bit; a stop asked for at sweep s takes effect after sweep s+1.  Inside
+    sweep s's callback the hyperparameter getter and timing().n_launch describe sweep s in
+    both modes, although with the pipeline sweep s+1's start has been queued by then."""
     tr, te = ml100k
     kw = dict(num_factor=30, seed=8, rng="philox", eval_train=True, quirks=quirks)
-    a = _run(tr, te, 6, **kw)
-    b = _run(tr, te, 6, pipeline=1, **kw)
+    runs = []
+    for extra in ({}, {"pipeline": 1}):
+        L = FMLearnSBPMF(**extra, **kw)
+        L.set_data(Data(*tr), Data(*te))
+        seen = []
+        L.learn(sweeps=6, callback=lambda h, L=L, seen=seen: seen.append((L.hyper(), int(L.timing().n_launch))))
+        runs.append((L, seen))
+    (a, seen_a), (b, seen_b) = runs
+    for L, seen in runs:
+        assert [hy["tau"] for hy, _ in seen] == [h["tau"] for h in L.history]
+    for (ha, na), (hb, nb) in zip(seen_a, seen_b):
+        for f in ("sigma_u", "mu_u", "sigma_v", "mu_v", "tau"):
+            assert np.array_equal(ha[f], hb[f]), f
+        assert na == nb
+    print("n_launch per sweep:", [n for _, n in seen_a], [n for _, n in seen_b])
+    for seen in (seen_a, seen_b):
+        assert len(seen) == 6 and len({n for _, n in seen[1:]}) == 1
     for f in ("sweep", "rmse_avg", "rmse_this", "rmse_train", "tau", "collected"):
         assert np.array_equal([h[f] for h in a.history], [h[f] for h in b.history]), f
     for x, y in zip(a.factors(), b.factors()):

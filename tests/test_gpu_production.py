@@ -150,7 +150,7 @@ def test_ml20m_k200_reference_stream_one_sweep():
 def test_prologue_overlap_is_bitwise_neutral(ml100k, quirks):
     """Throughput mode draws sweep s+1's hyperparameters at the end of sweep s,
     their kernels ahead of the test evaluation and the host draws while it runs
-    (sbmf.cpp run_sweeps_T).  The chain must be the one without the overlap
+    (sweep.cpp SweepRun).  The chain must be the one without the overlap
     (tune bit 26) bit for bit: across learn() calls of one sweep each (the
     bench's pattern), with residual recomputes on some sweeps, with biases, with
     hyper() reporting the sweep just run, and after set_factors (which drops the
