@@ -476,6 +476,72 @@ int sbmf_save_libfm_binary(const char* stem, const sbmf_ratings* in, uint32_t it
 int sbmf_save_triples(const char* path, const sbmf_ratings* in);
 void sbmf_free_ratings(sbmf_ratings* r);
 
+/* --- libFM cases with any number of features (the general MCMC / ALS learner) ---------------- */
+/* A libFM data set as data: a CSR by case.  Case c holds the features
+ * attr[ptr[c] .. ptr[c+1]) with the values x[] beside them (libFM's DATA_FLOAT,
+ * fm_data.h:25) and the target target[c]; a case may hold no feature.  num_attr
+ * is Data::num_feature (Data.h:220-222): the largest feature id + 1, or 0 for a
+ * set without features.  Within a case the entries are sorted by attribute id:
+ * the order libFM's in-memory transpose (Data::create_data_t) gives every
+ * per-case accumulation (add_main_q, predict_data_and_write_to_eterms).  An
+ * attribute repeated inside one case is refused (SBMF_E_ARG): the learner's
+ * passes write one {e, q} record per case of the attribute being drawn, and a
+ * repeat would make two entries of one row collide on it. */
+typedef struct sbmf_cases {
+    uint64_t n;        /* cases                                   */
+    uint64_t nnz;      /* features over all cases (= ptr[n])      */
+    uint32_t num_attr; /* largest feature id + 1 (0: no feature)  */
+    uint64_t* ptr;     /* [n + 1]                                 */
+    uint32_t* attr;    /* [nnz]                                   */
+    float* x;          /* [nnz]                                   */
+    float* target;     /* [n]                                     */
+} sbmf_cases;
+/* libFM text "target id:value id:value ..." with any number of features per
+ * line: Data::load's text branch (Data.h:173-283) with its acceptance rules
+ * (:192-217: leading blanks, empty and '#' lines skipped, anything unparsable
+ * an error naming the line), parsed by the threaded line-aligned parser of
+ * sbmf_load_libfm with the same number rules.  Entries come back sorted by id
+ * within each case (stable); a repeated id in one case is SBMF_E_ARG naming the
+ * line; a negative id is SBMF_E_IO.  Text only: libFM's binary files (.x / .xt)
+ * are read by the two-feature loaders above. */
+int sbmf_load_libfm_cases(const char* path, sbmf_cases* out);
+void sbmf_free_cases(sbmf_cases* c);
+/* The fewest contiguous id ranges [bounds[r], bounds[r+1]) covering [0, num_attr)
+ * such that no training case holds two attributes of one range (greedy over the
+ * ascending ids, linear in nnz; attributes without a training case never
+ * conflict).  draw_w / draw_v (fm_learn_mcmc.h:671-718, :780-835) touch the
+ * cache of the drawn attribute's cases only, so the attributes of one range
+ * commute exactly and libFM's ascending loop over them (:435-457, :555-577) is
+ * one launch.  Writes *nranges and, when bounds is non-NULL, bounds[0 ..
+ * *nranges]; SBMF_E_ARG when cap < *nranges + 1 (call with bounds = NULL to
+ * size it) or an attribute id is >= num_attr.  Host only. */
+int sbmf_fm_ranges(const sbmf_cases* train, uint32_t num_attr, uint32_t* bounds, uint32_t cap, uint32_t* nranges);
+/* The training / test cases of a SBMF_METHOD_LIBFM_MCMC or SBMF_METHOD_ALS
+ * context, in place of sbmf_set_train / sbmf_set_test (the arrays are copied;
+ * unsorted cases are sorted, a repeated attribute is SBMF_E_ARG).  Replaces
+ * Data::load + create_data_t for fm_learn_mcmc (libfm.cpp:140-171).  Any other
+ * method: SBMF_E_STATE naming it.  The learner (fm_learn_mcmc.h:411-623 on the
+ * GPU, csrc/fmg.cpp) then runs libFM's chain draw for draw over
+ * num_attribute = max(train, test num_attr) + 1 attributes (libfm.cpp:328), one
+ * launch per (range of sbmf_fm_ranges, row-length bin); sbmf_prepare, sbmf_run,
+ * sbmf_predict, sbmf_get_hyper and sbmf_get_timing work as for the
+ * two-attribute learner.  One rank: a context that joined a communicator or a
+ * virtual rank is SBMF_E_STATE at sbmf_prepare.  sbmf_get_factors /
+ * sbmf_get_biases on such a context are SBMF_E_STATE: the model is read with
+ * sbmf_get_fm.  SBMF_FMM_GENERAL=1 in the environment sends the triples of
+ * sbmf_set_train through this learner too (user u -> attribute u, item i ->
+ * num_users + i, x = 1), for tests and for measuring the price of generality;
+ * factors and biases are then read as for the two-attribute learner. */
+int sbmf_set_train_cases(sbmf_ctx* ctx, const sbmf_cases* cases);
+int sbmf_set_test_cases(sbmf_ctx* ctx, const sbmf_cases* cases);
+/* fm_model (fm_model.h:35-60) of the general learner: w0, w[num_attribute] and
+ * v[K][num_attribute] (f-major, as fm_model::v).  Any pointer may be NULL. */
+int sbmf_get_fm(sbmf_ctx* ctx, double* w0, double* w, double* v);
+/* num_attribute, the ranges of the training set, and the kernel launches of the
+ * last iteration (0 before the first).  Any pointer may be NULL.  SBMF_E_STATE
+ * on a context that does not run the general learner. */
+int sbmf_fm_info(sbmf_ctx* ctx, uint32_t* num_attr, uint32_t* nranges, uint32_t* launches_per_iter);
+
 /* --- multi-GPU layout (host only) ---------------------------------------------------------- */
 /* The row partition every rank uses: contiguous row blocks balanced by
  * ratings (ptr = CSR/CSC offsets [R+1]), boundaries rounded to 256 rows.

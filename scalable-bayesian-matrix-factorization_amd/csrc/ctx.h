@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "rng.h"
 #include "fmm.h"
+#include "fmg.h"
 #include "foldin.h"
 #include "recommend.h"
 #include "vbo.h"
@@ -254,6 +255,29 @@ struct sbmf_ctx {
     hipEvent_t fev[3] = {};
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
     FMLearner* fm = nullptr;  // -method mcmc --order libfm / als (fmm.cpp)
+    // the same chain on cases with any number of features (fmg.cpp): the host copies of
+    // sbmf_set_train_cases / sbmf_set_test_cases (or, with SBMF_FMM_GENERAL=1, the triples of
+    // sbmf_set_train restated as cases: fg_triples, the model then reads back by user / item)
+    struct HostCases {
+        std::vector<uint64_t> ptr;
+        std::vector<uint32_t> attr;
+        std::vector<float> x, y;
+        uint32_t num_attr = 0;
+        bool set = false;
+        sbmf_cases view() {
+            sbmf_cases c{};
+            c.n = y.size();
+            c.nnz = attr.size();
+            c.num_attr = num_attr;
+            c.ptr = ptr.data();
+            c.attr = attr.data();
+            c.x = x.data();
+            c.target = y.data();
+            return c;
+        }
+    } ctr, cte;
+    FGLearner* fg = nullptr;
+    bool fg_triples = false;
     ~sbmf_ctx();
 };
 

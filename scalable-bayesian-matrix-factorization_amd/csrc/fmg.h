@@ -1,0 +1,95 @@
+// fmg.h -- libFM's MCMC / ALS learner (fm_learn_mcmc.h:411-623 draw_all, :627-835
+// draw_w0 / draw_w / draw_v, :117-348 predict_data_and_write_to_eterms) for cases with any
+// number of features and real-valued x, on the GPU.  The two-attribute learner (fmm.h)
+// is built around "one user and one item per case"; this one keeps libFM's own cache:
+// one {e, q} record per training case (e_q_term), and the training set twice -- a
+// case-major CSR (q, predictions) and an attribute-major CSC of {case, x} entries
+// (libFM's data_t), cases ascending within an attribute.
+//
+// draw_w / draw_v read and write the cache of the drawn attribute's cases only, so two
+// attributes that share no case commute exactly.  sbmf_fm_ranges cuts [0, p) into
+// contiguous ranges of mutually exclusive attributes; libFM's ascending loop over a range
+// is one launch per row-length bin (each attribute with the normal libFM's order assigns
+// it), and the ranges run in ascending order.  A one-hot field is one range; a multi-hot
+// field degrades to ranges of one attribute, and the chain is still libFM's.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/sbmf.h"
+
+namespace sbmf {
+
+// One pass over the attribute rows of one (range, bin).  Row `a` owns the CSC entries
+// [aptr[a], aptr[a+1]); an entry is {case, bits of x (float)}.
+struct FGPassArgs {
+    const uint32_t* rows;   // [nrows] attributes of this launch
+    uint32_t nrows;
+    const uint32_t* aptr;   // [p+1]
+    const uint2* ent;       // [nnz] {case, x}
+    double2* eq;            // [n] {e, q} per training case (libFM's e_q_term)
+    double* own;            // w, or column f of v, by attribute
+    const double* z;        // normals, z[a * zs + zoff] (do_sample)
+    uint32_t zs, zoff;
+    double alpha, mu, lambda;
+    int do_sample;
+    // long rows in chunks (non-null: the launch runs over chunks {row, first entry, entries,
+    // long-row index}): xmode 1 writes chunk ri's {sum h e, sum h^2} to sums[ri]; xmode 2
+    // takes {old, new, keep} from delta[long-row index] and updates the chunk's cases;
+    // xmode 0: sums, draw and update in one pass
+    int xmode;
+    const uint4* chunks;
+    double2* sums;
+    const double4* delta;
+};
+// draw_w (:670-719) / draw_v (:780-835) over the rows of a launch, 64 / 256 / 1024 threads per row
+hipError_t fmg_wpass(const FGPassArgs& a, int threads_per_row, hipStream_t st);
+hipError_t fmg_vpass(const FGPassArgs& a, int threads_per_row, hipStream_t st);
+// long rows: row i of `rows` owns chunks [cfirst[i], cfirst[i+1]); chunk sums added in chunk
+// order, the draw, own written, delta[i] = {old, new, keep}
+hipError_t fmg_chunk_draw(const FGPassArgs& a, const uint32_t* rows, const uint32_t* cfirst, uint32_t nlong,
+                          const double2* csums, int vpass, double4* delta, hipStream_t st);
+// eq[c].q = sum over the case's entries (ascending attribute) of v_f[attr] * x  (add_main_q, :513-517)
+hipError_t fmg_q(const uint32_t* cptr, const uint32_t* cattr, const float* cx, uint64_t n, const double* vf,
+                 double2* eq, hipStream_t st);
+// part[b] = {sum e^2, sum (e - w0)} over 1024-case blocks of eq[].e; eq[c].e -= d
+hipError_t fmg_esums(const double2* eq, uint64_t n, double w0, double* part, hipStream_t st);
+hipError_t fmg_shift(double2* eq, uint64_t n, double d, hipStream_t st);
+// predict_data_and_write_to_eterms (:117-348) per case in its accumulation order.  Train
+// (eq non-null): eq[c] = {pred - y, 0}, part[b] = sum (clamp(pred) - y)^2.  Test: pthis[t] =
+// pred, sum_all[t] += clamp(pred), part[2b] = (clamp(sum_all / it1) - y)^2, part[2b+1] =
+// (clamp(pred) - y)^2.
+struct FGPredictArgs {
+    const uint32_t* cptr;
+    const uint32_t* cattr;
+    const float* cx;
+    const float* y;
+    uint64_t n;
+    const double* vT;  // [p][Kp]
+    const double* w;   // [p]
+    double w0;
+    uint32_t K, Kp;
+    int k0, k1;
+    double lo, hi;
+};
+hipError_t fmg_predict_train(const FGPredictArgs& a, double2* eq, double* part, hipStream_t st);
+hipError_t fmg_predict_test(const FGPredictArgs& a, double it1, double* pthis, double* sum_all, double* part,
+                            hipStream_t st);
+
+// ---- host learner (fmg.cpp), driven by the C ABI in sbmf.cpp
+struct FGLearner;
+FGLearner* fmg_create(const sbmf_config& c, const sbmf_cases& train, const sbmf_cases& test, hipStream_t st);
+void fmg_destroy(FGLearner* L);
+void fmg_run(FGLearner* L, uint32_t iters, sbmf_sweep_cb cb, void* user);
+void fmg_predict_out(FGLearner* L, double* out);
+void fmg_model(FGLearner* L, double* w0, double* w, double* v);  // w[p], v[K][p]
+void fmg_hyper_out(FGLearner* L, double* h4k, double* alpha);    // as fmm_hyper_out
+uint32_t fmg_launches(const FGLearner* L);
+uint32_t fmg_num_attribute(const FGLearner* L);
+uint32_t fmg_num_ranges(const FGLearner* L);
+// the ranges of sbmf_fm_ranges over [0, p) (train cases; ids >= train.num_attr have no case)
+void fm_ranges(const sbmf_cases& train, uint32_t p, std::vector<uint32_t>& bounds);
+
+}  // namespace sbmf

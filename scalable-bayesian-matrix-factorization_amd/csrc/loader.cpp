@@ -612,7 +612,8 @@ int load_x(const std::string& xf, const std::string& yf, uint32_t item_offset, s
     auto bad_row = [&](uint64_t row) {
         g_lerr = xf + " row " + std::to_string(row) +
                  ": the SBPMF sampler needs exactly one user and one item feature per row" +
-                 (item_offset > 0 ? " (user id < item_offset <= item id)" : "");
+                 (item_offset > 0 ? " (user id < item_offset <= item id)" : "") +
+                 "; cases with any other number of features are read from libFM text only (sbmf_load_libfm_cases)";
         sbmf_free_ratings(out);
         return SBMF_E_IO;
     };
@@ -834,7 +835,8 @@ int load_xt(const std::string& xf, const std::string& yf, uint32_t item_offset, 
         if (c != UINT64_MAX) {
             g_lerr = xf + " case " + std::to_string(c) + ": the learners need exactly one user and one item feature "
                      "per case (" + std::to_string(cnt[c].load()) + " features" +
-                     (item_offset > 0 ? "; user id < item_offset <= item id)" : ")");
+                     (item_offset > 0 ? "; user id < item_offset <= item id)" : ")") +
+                     "; cases with any other number of features are read from libFM text only (sbmf_load_libfm_cases)";
             sbmf_free_ratings(out);
             return SBMF_E_IO;
         }
@@ -993,5 +995,213 @@ void sbmf_free_ratings(sbmf_ratings* r) {
 }
 
 const char* sbmf_loader_error(void) { return g_lerr.c_str(); }
+
+}  // extern "C"
+
+// ---- libFM text with any number of features per line (sbmf_cases): Data::load's text
+// branch (Data.h:173-283).  The same line-aligned chunks on threads as run_chunks, each
+// chunk into vectors of its own, concatenated in file order.
+namespace {
+
+struct CasePart {
+    std::vector<uint32_t> len, attr;  // features per case; the entries, case after case
+    std::vector<float> x, y;
+    size_t lines = 0;
+    long err_line = -1;
+    int err_code = SBMF_E_IO;
+    std::string err;
+    uint32_t max_attr = 0;
+    bool any = false;
+};
+
+// the entries pushed since `from`, sorted by id (stable); false on a repeated id
+bool sort_case(CasePart& P, size_t from) {
+    const size_t m = P.attr.size() - from;
+    uint32_t* a = P.attr.data() + from;
+    float* v = P.x.data() + from;
+    bool sorted = true;
+    for (size_t k = 1; k < m && sorted; ++k) sorted = a[k - 1] < a[k];
+    if (sorted) return true;
+    for (size_t k = 1; k < m; ++k) {  // insertion sort: stable, lines are short
+        const uint32_t ka = a[k];
+        const float kv = v[k];
+        size_t j = k;
+        for (; j > 0 && a[j - 1] > ka; --j) {
+            a[j] = a[j - 1];
+            v[j] = v[j - 1];
+        }
+        a[j] = ka;
+        v[j] = kv;
+    }
+    for (size_t k = 1; k < m; ++k)
+        if (a[k - 1] == a[k]) return false;
+    return true;
+}
+
+bool case_done(CasePart& P, size_t from, float target) {
+    if (!sort_case(P, from)) {
+        P.err_code = SBMF_E_ARG;
+        P.err = "an attribute id is repeated inside one case (the learner writes one record per case of a row):";
+        return false;
+    }
+    for (size_t k = from; k < P.attr.size(); ++k) P.max_attr = std::max(P.max_attr, P.attr[k]);
+    P.any = P.any || P.attr.size() > from;
+    P.len.push_back((uint32_t)(P.attr.size() - from));
+    P.y.push_back(target);
+    return true;
+}
+
+// fast path over [p, le): short decimals and ids; false = take the slow path (nothing kept)
+bool cases_line_fast(CasePart& P, const char* p, const char* le) {
+    const char* q = p;
+    while (q < le && (*q == ' ' || *q == '\t')) ++q;
+    if (q == le || *q == '#' || *q == '\r') return true;
+    float target;
+    const char* e;
+    if (!parse_fast(q, target, e)) return false;
+    q = e;
+    const size_t from = P.attr.size();
+    for (;;) {
+        const char* b = q;
+        while (q < le && (*q == ' ' || *q == '\t')) ++q;
+        if (q >= le || *q == '#' || *q == '\r') break;
+        unsigned id;
+        float fv;
+        if (q == b || !parse_uint(q, id) || id > 0x7fffffffu || q >= le || *q != ':' ||
+            !parse_fast(q + 1, fv, e)) {
+            P.attr.resize(from);
+            P.x.resize(from);
+            return false;
+        }
+        q = e;
+        P.attr.push_back(id);
+        P.x.push_back(fv);
+    }
+    if (!case_done(P, from, target)) {
+        P.attr.resize(from);
+        P.x.resize(from);
+        return false;  // the slow path reports it
+    }
+    return true;
+}
+
+// the reference's rule on a terminated copy of the line (sscanf "%f", then "%d:%f" pairs)
+bool cases_line_slow(CasePart& P, const char* t) {
+    const char* q = t;
+    while (*q == ' ' || *q == '\t') ++q;
+    if (*q == 0 || *q == '#' || *q == '\r') return true;
+    char* e;
+    const float target = std::strtof(q, &e);
+    if (e == q) return P.err = "cannot parse libFM", false;
+    q = e;
+    const size_t from = P.attr.size();
+    while (true) {
+        while (*q == ' ' || *q == '\t') ++q;
+        if (*q == 0 || *q == '#' || *q == '\r') break;
+        char* e1;
+        const long id = std::strtol(q, &e1, 10);
+        if (e1 == q || *e1 != ':') return P.err = "cannot parse libFM", false;
+        q = e1 + 1;
+        char* e3;
+        const float fv = std::strtof(q, &e3);
+        if (e3 == q) return P.err = "cannot parse libFM", false;
+        q = e3;
+        if (id < 0 || id > 0x7fffffffl) return P.err = "feature id out of range [0, 2^31) in libFM", false;
+        P.attr.push_back((uint32_t)id);
+        P.x.push_back(fv);
+    }
+    return case_done(P, from, target);
+}
+
+void parse_cases(CasePart& P, const char* p, const char* const end) {
+    std::string tmp;
+    while (p < end) {
+        const char* nl = static_cast<const char*>(std::memchr(p, '\n', (size_t)(end - p)));
+        const char* le = nl ? nl : end;
+        const size_t lineno = P.lines++;
+        if (!nl || !cases_line_fast(P, p, le)) {
+            tmp.assign(p, le);
+            if (!cases_line_slow(P, tmp.c_str())) {
+                P.err_line = (long)lineno;
+                return;
+            }
+        }
+        p = le + 1;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+void sbmf_free_cases(sbmf_cases* c) {
+    if (!c) return;
+    std::free(c->ptr);
+    std::free(c->attr);
+    std::free(c->x);
+    std::free(c->target);
+    std::memset(c, 0, sizeof *c);
+}
+
+int sbmf_load_libfm_cases(const char* path, sbmf_cases* out) {
+    if (!path || !out) return SBMF_E_ARG;
+    std::memset(out, 0, sizeof *out);
+    InFile f;
+    if (!open_in(path, f)) {
+        g_lerr = std::string("unable to open ") + path;
+        return SBMF_E_IO;
+    }
+    size_t min_bytes = 4u << 20;  // SBMF_LOAD_CHUNK: smaller chunks (tests)
+    if (const char* e = std::getenv("SBMF_LOAD_CHUNK")) min_bytes = (size_t)std::max(1L, std::atol(e));
+    const std::vector<size_t> cut = line_chunks(f.p, f.n, min_bytes);
+    const size_t nc = cut.size() - 1;
+    std::vector<CasePart> parts(nc);
+    parallel_for(nc, [&](size_t c) { parse_cases(parts[c], f.p + cut[c], f.p + cut[c + 1]); });
+    size_t before = 0, n = 0, nnz = 0;
+    uint32_t mx = 0;
+    bool any = false;
+    for (const CasePart& p : parts) {
+        if (p.err_line >= 0) {
+            g_lerr = p.err + " line " + std::to_string(before + (size_t)p.err_line + 1) + " of " + path;
+            return p.err_code;
+        }
+        before += p.lines;
+        n += p.len.size();
+        nnz += p.attr.size();
+        mx = std::max(mx, p.max_attr);
+        any = any || p.any;
+    }
+    out->ptr = static_cast<uint64_t*>(big_alloc((n + 1) * sizeof(uint64_t)));
+    out->attr = static_cast<uint32_t*>(big_alloc(std::max<size_t>(nnz, 1) * sizeof(uint32_t)));
+    out->x = static_cast<float*>(big_alloc(std::max<size_t>(nnz, 1) * sizeof(float)));
+    out->target = static_cast<float*>(big_alloc(std::max<size_t>(n, 1) * sizeof(float)));
+    if (!out->ptr || !out->attr || !out->x || !out->target) {
+        sbmf_free_cases(out);
+        return SBMF_E_NOMEM;
+    }
+    std::vector<size_t> c0(nc + 1, 0), e0(nc + 1, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        c0[c + 1] = c0[c] + parts[c].len.size();
+        e0[c + 1] = e0[c] + parts[c].attr.size();
+    }
+    parallel_for(nc, [&](size_t c) {
+        const CasePart& p = parts[c];
+        uint64_t at = e0[c];
+        for (size_t k = 0; k < p.len.size(); ++k) {
+            out->ptr[c0[c] + k] = at;
+            at += p.len[k];
+        }
+        if (!p.attr.empty()) {
+            std::memcpy(out->attr + e0[c], p.attr.data(), p.attr.size() * sizeof(uint32_t));
+            std::memcpy(out->x + e0[c], p.x.data(), p.x.size() * sizeof(float));
+        }
+        if (!p.y.empty()) std::memcpy(out->target + c0[c], p.y.data(), p.y.size() * sizeof(float));
+    });
+    out->ptr[n] = nnz;
+    out->n = n;
+    out->nnz = nnz;
+    out->num_attr = any ? mx + 1 : 0;
+    return SBMF_OK;
+}
 
 }  // extern "C"

@@ -34,6 +34,7 @@ Audit& audit() {
 sbmf_ctx::~sbmf_ctx() {
     vbo_destroy(vb);
     fmm_destroy(fm);
+    fmg_destroy(fg);
     using namespace sbmf;
     pinned_free(h_pinned, h_pinned_bytes);
     pinned_free(h_pre, h_pre_bytes);
@@ -308,7 +309,48 @@ void sbmf_destroy(sbmf_ctx* ctx) {
 // The learner's set-up for the data given so far.  Every learner's dims: max id + 1 over train
 // and test (gibbs_sbpmf_final.cpp:146-148), or sbmf_set_dims; for -method mcmc --order libfm / als
 // I is the item attribute offset of the users-first layout
+static bool libfm_method(const sbmf_ctx* c) {
+    return c->cfg.method == SBMF_METHOD_LIBFM_MCMC || c->cfg.method == SBMF_METHOD_ALS;
+}
+
+// The general learner (fmg.cpp) on the cases given so far: one rank only
+static void prepare_cases(sbmf_ctx* c) {
+    if (c->nranks > 1 || c->virt || c->comm != &c->own_comm || c->own_comm.active())
+        sbmf::fail(SBMF_E_STATE, "the general libFM learner (cases with any number of features) runs on one rank: "
+                                 "this context joined a communicator or is a virtual rank");
+    c->K = c->cfg.num_factor;
+    c->fg = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st);
+    c->prepared = true;
+}
+
+// SBMF_FMM_GENERAL=1: the triples as cases {user u -> attribute u, item i -> I + i, x = 1}
+static void triples_to_cases(const std::vector<uint32_t>& u, const std::vector<uint32_t>& i, const std::vector<double>& r,
+                             uint32_t I, sbmf_ctx::HostCases& out) {
+    const size_t n = u.size();
+    out.ptr.resize(n + 1);
+    out.attr.resize(2 * n);
+    out.x.assign(2 * n, 1.0f);
+    out.y.resize(n);
+    uint32_t mx = 0;
+    for (size_t q = 0; q < n; ++q) {
+        if ((uint64_t)I + i[q] > 0xfffffffdull) sbmf::fail(SBMF_E_ARG, "attribute id too large");
+        out.ptr[q] = 2 * q;
+        out.attr[2 * q] = u[q];
+        out.attr[2 * q + 1] = I + i[q];
+        mx = std::max(mx, I + i[q]);
+        out.y[q] = (float)r[q];
+    }
+    out.ptr[n] = 2 * n;
+    out.num_attr = n ? mx + 1 : 0;
+    out.set = true;
+}
+
 static void prepare_ctx(sbmf_ctx* c) {
+    if (c->ctr.set) {
+        prepare_cases(c);
+        return;
+    }
+    if (c->cte.set) sbmf::fail(SBMF_E_STATE, "sbmf_set_test_cases without sbmf_set_train_cases");
     if (c->tu.empty()) sbmf::fail(SBMF_E_STATE, "no training data (sbmf_set_train)");
     uint32_t umax = 0, imax = 0;
     for (size_t x = 0; x < c->tu.size(); ++x) {
@@ -327,6 +369,14 @@ static void prepare_ctx(sbmf_ctx* c) {
         return;
     }
     sbmf::Comm* comm = c->nranks > 1 ? c->comm : nullptr;
+    const char* gen = std::getenv("SBMF_FMM_GENERAL");
+    if (libfm_method(c) && gen && std::atoi(gen) != 0) {
+        triples_to_cases(c->tu, c->ti, c->tr, c->I, c->ctr);
+        triples_to_cases(c->su, c->si, c->sr, c->I, c->cte);
+        c->fg_triples = true;
+        prepare_cases(c);
+        return;
+    }
     if (c->cfg.method == SBMF_METHOD_VB)
         c->vb = vbo_create(c->cfg, c->tu.size(), c->tu.data(), c->ti.data(), c->tr.data(), c->su.size(), c->su.data(),
                            c->si.data(), c->sr.data(), c->I, c->J, c->st, comm);
@@ -348,6 +398,7 @@ int sbmf_set_train(sbmf_ctx* ctx, uint64_t n, const uint32_t* user, const uint32
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (ctx->prepared) sbmf::fail(SBMF_E_STATE, "data already prepared");
+    if (ctx->ctr.set || ctx->cte.set) sbmf::fail(SBMF_E_STATE, "the context already holds cases (sbmf_set_train_cases)");
     set_triples(n, user, item, rating, ctx->tu, ctx->ti, ctx->tr);
     API_END(ctx)
 }
@@ -356,7 +407,114 @@ int sbmf_set_test(sbmf_ctx* ctx, uint64_t n, const uint32_t* user, const uint32_
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (ctx->prepared) sbmf::fail(SBMF_E_STATE, "data already prepared");
+    if (ctx->ctr.set || ctx->cte.set) sbmf::fail(SBMF_E_STATE, "the context already holds cases (sbmf_set_test_cases)");
     set_triples(n, user, item, rating, ctx->su, ctx->si, ctx->sr);
+    API_END(ctx)
+}
+
+// the caller's cases, copied: entries sorted by attribute within a case (stable), a repeat refused
+static void set_cases(const sbmf_cases* in, sbmf_ctx::HostCases& out, const char* fn) {
+    if (!in) sbmf::fail(SBMF_E_ARG, "%s: null cases", fn);
+    if ((in->n && (!in->ptr || !in->target)) || (in->nnz && (!in->attr || !in->x)))
+        sbmf::fail(SBMF_E_ARG, "%s: null array", fn);
+    if (in->n && (in->ptr[0] != 0 || in->ptr[in->n] != in->nnz))
+        sbmf::fail(SBMF_E_ARG, "%s: ptr must run from 0 to nnz", fn);
+    sbmf_ctx::HostCases h;
+    h.ptr.assign(in->n + 1, 0);
+    if (in->n) h.ptr.assign(in->ptr, in->ptr + in->n + 1);
+    h.attr.assign(in->attr, in->attr + in->nnz);
+    h.x.assign(in->x, in->x + in->nnz);
+    h.y.assign(in->target, in->target + in->n);
+    h.num_attr = in->num_attr;
+    std::vector<std::pair<uint32_t, float>> tmp;
+    for (uint64_t c = 0; c < in->n; ++c) {
+        const uint64_t b = h.ptr[c], e = h.ptr[c + 1];
+        if (e < b || e > in->nnz) sbmf::fail(SBMF_E_ARG, "%s: ptr decreases at case %llu", fn, (unsigned long long)c);
+        bool sorted = true;
+        for (uint64_t k = b; k < e; ++k) {
+            if (h.attr[k] >= in->num_attr)
+                sbmf::fail(SBMF_E_ARG, "%s: case %llu holds attribute %u >= num_attr %u", fn, (unsigned long long)c,
+                           h.attr[k], in->num_attr);
+            if (k > b && h.attr[k - 1] >= h.attr[k]) sorted = false;
+        }
+        if (sorted) continue;
+        tmp.clear();
+        for (uint64_t k = b; k < e; ++k) tmp.emplace_back(h.attr[k], h.x[k]);
+        std::stable_sort(tmp.begin(), tmp.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
+        for (uint64_t k = b; k < e; ++k) {
+            h.attr[k] = tmp[k - b].first;
+            h.x[k] = tmp[k - b].second;
+            if (k > b && h.attr[k - 1] == h.attr[k])
+                sbmf::fail(SBMF_E_ARG, "%s: case %llu repeats attribute %u (the learner writes one record per case of "
+                                       "a row)", fn, (unsigned long long)c, h.attr[k]);
+        }
+    }
+    h.set = true;
+    out = std::move(h);
+}
+
+static void check_cases_ctx(sbmf_ctx* ctx, const char* fn) {
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (ctx->prepared) sbmf::fail(SBMF_E_STATE, "data already prepared");
+    static const char* const names[] = {"mcmc (the SBPMF sampler)", "vb (online VB)", "mcmc, libFM order", "als"};
+    if (!libfm_method(ctx))
+        sbmf::fail(SBMF_E_STATE, "%s: cases with any number of features are read by libFM's MCMC / ALS learner "
+                                 "(SBMF_METHOD_LIBFM_MCMC, SBMF_METHOD_ALS) only; this context runs method %s",
+                   fn, names[ctx->cfg.method]);
+    if (!ctx->tu.empty() || !ctx->su.empty())
+        sbmf::fail(SBMF_E_STATE, "%s: the context already holds triples (sbmf_set_train / sbmf_set_test)", fn);
+}
+
+int sbmf_set_train_cases(sbmf_ctx* ctx, const sbmf_cases* cases) {
+    API_BEGIN
+    check_cases_ctx(ctx, "sbmf_set_train_cases");
+    set_cases(cases, ctx->ctr, "sbmf_set_train_cases");
+    API_END(ctx)
+}
+
+int sbmf_set_test_cases(sbmf_ctx* ctx, const sbmf_cases* cases) {
+    API_BEGIN
+    check_cases_ctx(ctx, "sbmf_set_test_cases");
+    set_cases(cases, ctx->cte, "sbmf_set_test_cases");
+    API_END(ctx)
+}
+
+int sbmf_get_fm(sbmf_ctx* ctx, double* w0, double* w, double* v) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
+    if (!ctx->fg) sbmf::fail(SBMF_E_STATE, "sbmf_get_fm: this context does not run the general libFM learner");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    fmg_model(ctx->fg, w0, w, v);
+    API_END(ctx)
+}
+
+int sbmf_fm_info(sbmf_ctx* ctx, uint32_t* num_attr, uint32_t* nranges, uint32_t* launches_per_iter) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
+    if (!ctx->fg) sbmf::fail(SBMF_E_STATE, "sbmf_fm_info: this context does not run the general libFM learner");
+    if (num_attr) *num_attr = fmg_num_attribute(ctx->fg);
+    if (nranges) *nranges = fmg_num_ranges(ctx->fg);
+    if (launches_per_iter) *launches_per_iter = fmg_launches(ctx->fg);
+    API_END(ctx)
+}
+
+int sbmf_fm_ranges(const sbmf_cases* train, uint32_t num_attr, uint32_t* bounds, uint32_t cap, uint32_t* nranges) {
+    sbmf_ctx* ctx = nullptr;
+    API_BEGIN
+    if (!train || !nranges) sbmf::fail(SBMF_E_ARG, "null argument");
+    if ((train->n && !train->ptr) || (train->nnz && !train->attr)) sbmf::fail(SBMF_E_ARG, "null array");
+    if (train->n && train->ptr[train->n] != train->nnz) sbmf::fail(SBMF_E_ARG, "ptr[n] != nnz");
+    for (uint64_t k = 0; k < train->nnz; ++k)
+        if (train->attr[k] >= num_attr) sbmf::fail(SBMF_E_ARG, "attribute %u >= num_attr %u", train->attr[k], num_attr);
+    std::vector<uint32_t> b;
+    sbmf::fm_ranges(*train, num_attr, b);
+    *nranges = (uint32_t)b.size() - 1;
+    if (bounds) {
+        if (cap < b.size()) sbmf::fail(SBMF_E_ARG, "bounds holds %u values, %zu needed", cap, b.size());
+        std::copy(b.begin(), b.end(), bounds);
+    }
     API_END(ctx)
 }
 
@@ -396,6 +554,12 @@ int sbmf_run(sbmf_ctx* ctx, uint32_t sweeps, sbmf_sweep_cb cb, void* user) {
         ctx->timing.ms_vb_factor = vbo_factor_ms(ctx->vb);
         return SBMF_OK;
     }
+    if (ctx->fg) {
+        fmg_run(ctx->fg, sweeps, cb, user);
+        ctx->timing = sbmf_timing{};
+        ctx->timing.n_launch = fmg_launches(ctx->fg);
+        return SBMF_OK;
+    }
     if (ctx->fm) {
         fmm_run(ctx->fm, sweeps, cb, user);
         ctx->timing = sbmf_timing{};
@@ -413,6 +577,10 @@ int sbmf_predict(sbmf_ctx* ctx, double* out) {
     HIPCHK(hipSetDevice(ctx->cfg.device));
     if (ctx->vb) {
         vbo_predict_out(ctx->vb, out);
+        return SBMF_OK;
+    }
+    if (ctx->fg) {
+        fmg_predict_out(ctx->fg, out);
         return SBMF_OK;
     }
     if (ctx->fm) {
@@ -439,6 +607,21 @@ int sbmf_get_factors(sbmf_ctx* ctx, double* U, double* V) {
         vbo_factors(ctx->vb, U, V);
         return SBMF_OK;
     }
+    if (ctx->fg) {
+        if (!ctx->fg_triples)
+            sbmf::fail(SBMF_E_STATE, "a context given cases has no user / item tables: read the model with sbmf_get_fm");
+        // SBMF_FMM_GENERAL: v of the users [I][K] and items [J][K]; items past the attribute count read 0
+        const uint32_t p = fmg_num_attribute(ctx->fg), K = ctx->K, I = ctx->I;
+        std::vector<double> h((size_t)K * p);
+        fmg_model(ctx->fg, nullptr, nullptr, h.data());
+        for (uint32_t f = 0; f < K; ++f) {
+            if (U)
+                for (uint32_t a = 0; a < I; ++a) U[(size_t)a * K + f] = h[(size_t)f * p + a];
+            if (V)
+                for (uint32_t a = 0; a < ctx->J; ++a) V[(size_t)a * K + f] = I + a < p ? h[(size_t)f * p + I + a] : 0.0;
+        }
+        return SBMF_OK;
+    }
     if (ctx->fm) {
         fmm_factors(ctx->fm, U, V);
         return SBMF_OK;
@@ -452,7 +635,8 @@ int sbmf_set_factors(sbmf_ctx* ctx, const double* U, const double* V) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
-    if (ctx->vb || ctx->fm) sbmf::fail(SBMF_E_STATE, "sbmf_set_factors is not supported by the VB / libFM learners");
+    if (ctx->vb || ctx->fm || ctx->fg)
+        sbmf::fail(SBMF_E_STATE, "sbmf_set_factors is not supported by the VB / libFM learners");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->st));
     ctx->pre.valid = false;  // hyperparameters drawn ahead from the old tables
@@ -468,6 +652,10 @@ int sbmf_get_hyper(sbmf_ctx* ctx, double* h, double* tau) {
     if (ctx->vb) {
         HIPCHK(hipSetDevice(ctx->cfg.device));
         vbo_hyper_out(ctx->vb, h, tau);
+        return SBMF_OK;
+    }
+    if (ctx->fg) {
+        fmg_hyper_out(ctx->fg, h, tau);
         return SBMF_OK;
     }
     if (ctx->fm) {
@@ -495,6 +683,17 @@ int sbmf_get_biases(sbmf_ctx* ctx, double* bu, double* bv, double* b0) {
         vbo_biases(ctx->vb, bu, bv, b0);
         return SBMF_OK;
     }
+    if (ctx->fg) {
+        if (!ctx->fg_triples)
+            sbmf::fail(SBMF_E_STATE, "a context given cases has no user / item biases: read the model with sbmf_get_fm");
+        const uint32_t p = fmg_num_attribute(ctx->fg), I = ctx->I;
+        std::vector<double> h(p);
+        fmg_model(ctx->fg, b0, h.data(), nullptr);
+        if (bu) std::copy(h.begin(), h.begin() + I, bu);
+        if (bv)
+            for (uint32_t a = 0; a < ctx->J; ++a) bv[a] = I + a < p ? h[I + a] : 0.0;
+        return SBMF_OK;
+    }
     if (ctx->fm) {  // libFM's w (users, items) and w0
         fmm_biases(ctx->fm, bu, bv, b0);
         return SBMF_OK;
@@ -512,8 +711,9 @@ int sbmf_get_dims(sbmf_ctx* ctx, uint32_t* nu, uint32_t* ni, uint64_t* ntr, uint
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (nu) *nu = ctx->I;
     if (ni) *ni = ctx->J;
-    if (ntr) *ntr = ctx->tu.size();
-    if (nte) *nte = ctx->su.size();
+    const bool cases = ctx->ctr.set && !ctx->fg_triples;  // given as cases: no user / item dims
+    if (ntr) *ntr = cases ? ctx->ctr.y.size() : ctx->tu.size();
+    if (nte) *nte = cases ? ctx->cte.y.size() : ctx->su.size();
     API_END(ctx)
 }
 

@@ -7,6 +7,9 @@
 // flags are libFM's (libfm.cpp:86-111) plus the sampler's own settings.
 // Output follows fm_learn_mcmc_simultaneous.h: per sweep
 //   "#Iter=%3d\tTrain=<rmse>\tTest=<rmse>"                      (:244)
+// -method mcmc (libFM order) and -method als read libFM text with any number of features per
+// case (sbmf_load_libfm_cases -> the general learner, fmg.cpp); a file of "user:1 item:1"
+// cases takes the two-attribute learner.
 // and the file test_rmse_<k0><k1><K>_<method> (truncated at start, one
 // running-mean test RMSE per line, :57-62,146); -out writes one averaged
 // prediction per test line (libfm.cpp:629-634).
@@ -521,16 +524,48 @@ int main(int argc, char** argv) {
         uint32_t off = (uint32_t)cl.getl("item_offset", 0);
         std::cout << "Loading train...\t" << std::endl;
         sbmf_ratings tr{}, te{};
-        load(cl.get("train", ""), fmt, off, has_x, tr);
+        // A libFM text file whose cases are not all "one user and one item feature" is a general file:
+        // libFM's MCMC / ALS learner reads it as cases with any number of features (sbmf_cases, fmg.cpp);
+        // a two-feature file takes the path it always took.  Binary stems keep the two-feature loaders.
+        const bool text_input = libfm_input && fmt != "binary" && !has_binary(trainf, has_x) && !rowmajor_only(trainf);
+        bool general = false;
+        auto load_or_general = [&](const std::string& path, sbmf_ratings& r) {
+            try {
+                load(path, fmt, off, has_x, r);
+            } catch (const std::runtime_error& e) {
+                if (!text_input || !std::strstr(e.what(), "exactly one user and one item feature per line")) throw;
+                general = true;
+            }
+        };
+        load_or_general(cl.get("train", ""), tr);
         std::cout << "Loading test... \t" << std::endl;
-        load(cl.get("test", ""), fmt, off, has_x, te);
+        load_or_general(cl.get("test", ""), te);
+        sbmf_cases ctr{}, cte{};
+        if (general) {
+            // refused before any learning: only libFM's own chain is defined on such cases
+            const char* why = nullptr;
+            if (rec || recg)
+                why = "-recommend / -recommend_guests rank the items of the SBPMF sampler's user x item model";
+            else if (vb)
+                why = "-method vb (online VB) updates one user and one item attribute per case";
+            else if (!lfm)
+                why = "-order sbpmf (the SBPMF sampler) factorizes a user x item rating matrix";
+            if (why)
+                throw std::runtime_error(std::string("the input holds cases that are not one user and one item feature; ") +
+                                         why + ": use -method mcmc (libFM order) or -method als on such a file");
+            sbmf_free_ratings(&tr);
+            sbmf_free_ratings(&te);
+            if (sbmf_load_libfm_cases(cl.get("train", "").c_str(), &ctr) != SBMF_OK ||
+                sbmf_load_libfm_cases(cl.get("test", "").c_str(), &cte) != SBMF_OK)
+                throw std::runtime_error(sbmf_loader_error());
+        }
         // libFM's learners (fm_learn_mcmc, fm_learn_vb_online) take the file's feature ids as
         // their attribute ids: num_user = max first feature id + 1 over train and test
         // (libfm.cpp:219-221,263-265,375) and num_all_attribute = max feature id + 1 (:328).
         // With one user and one item feature per line that is the users-first layout with
         // item offset num_user, so no flag is needed (-item_offset overrides it).
         // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
-        if ((lfm || vb || rec || recg) && libfm_input && !cl.has("item_offset")) off = users_first_offset(tr, te);
+        if ((lfm || vb || rec || recg) && libfm_input && !cl.has("item_offset") && !general) off = users_first_offset(tr, te);
         std::vector<uint32_t> rec_ids;
         if (rec) {
             std::ifstream f(cl.get("rec_users", ""));
@@ -581,17 +616,33 @@ int main(int argc, char** argv) {
         auto chk = [&](int rc) {
             if (rc != SBMF_OK) throw std::runtime_error(sbmf_last_error(ctx));
         };
-        chk(sbmf_set_train(ctx, tr.n, tr.user, tr.item, tr.rating));
-        chk(sbmf_set_test(ctx, te.n, te.user, te.item, te.rating));
-        // libFM's attributes are the file's feature ids: users first, items from the
-        // (inferred or given) item offset on
-        if ((lfm || vb) && off) chk(sbmf_set_dims(ctx, off, 0));
+        std::vector<double> te_y;  // general input: the test targets as the -rlog evaluation reads them
+        if (general) {
+            chk(sbmf_set_train_cases(ctx, &ctr));
+            chk(sbmf_set_test_cases(ctx, &cte));
+            te_y.assign(cte.target, cte.target + cte.n);
+            te.n = cte.n;
+            te.rating = te_y.data();
+        } else {
+            chk(sbmf_set_train(ctx, tr.n, tr.user, tr.item, tr.rating));
+            chk(sbmf_set_test(ctx, te.n, te.user, te.item, te.rating));
+            // libFM's attributes are the file's feature ids: users first, items from the
+            // (inferred or given) item offset on
+            if ((lfm || vb) && off) chk(sbmf_set_dims(ctx, off, 0));
+        }
         chk(sbmf_prepare(ctx));
         uint32_t nu, ni;
         uint64_t ntr, nte;
         chk(sbmf_get_dims(ctx, &nu, &ni, &ntr, &nte));
-        std::cout << "#users=" << nu << "\t#items=" << ni << "\t#train=" << ntr << "\t#test=" << nte << "\tK=" << cfg.num_factor
-                  << std::endl;
+        if (general) {
+            uint32_t na = 0, nr = 0;
+            chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
+            std::cout << "#attributes=" << na << "\t#ranges=" << nr << "\t#train=" << ntr << "\t#test=" << nte
+                      << "\tK=" << cfg.num_factor << std::endl;
+        } else {
+            std::cout << "#users=" << nu << "\t#items=" << ni << "\t#train=" << ntr << "\t#test=" << nte
+                      << "\tK=" << cfg.num_factor << std::endl;
+        }
 
         RunState rs;
         std::ostringstream nm;
@@ -605,7 +656,10 @@ int main(int argc, char** argv) {
         rs.ctx = ctx;
         rs.test = &te;
         rs.avg_collected = !lfm && (cfg.average == 1 || (cfg.average == 0 && cfg.quirks == SBMF_QUIRKS_NONE));  // sbmf.cpp avg_collected
-        if (lfm) {  // libFM clamps to the train target range (libfm.cpp:459-460)
+        if (general) {
+            rs.lo = *std::min_element(ctr.target, ctr.target + ctr.n);
+            rs.hi = *std::max_element(ctr.target, ctr.target + ctr.n);
+        } else if (lfm) {  // libFM clamps to the train target range (libfm.cpp:459-460)
             rs.lo = *std::min_element(tr.rating, tr.rating + tr.n);
             rs.hi = *std::max_element(tr.rating, tr.rating + tr.n);
         } else {
@@ -668,8 +722,11 @@ int main(int argc, char** argv) {
             for (double p : pred) out << p << "\n";
         }
         sbmf_destroy(ctx);
+        if (general) te = sbmf_ratings{};  // its targets were te_y's
         sbmf_free_ratings(&tr);
         sbmf_free_ratings(&te);
+        sbmf_free_cases(&ctr);
+        sbmf_free_cases(&cte);
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return leave(1);

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "load_libfm_cases", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -70,6 +70,70 @@ class Data:
     @property
     def target(self):
         return self.rating
+
+
+class Cases:
+    """A libFM data set with any number of features per case (sbmf_cases): a CSR by case.
+    Case c holds the attributes attr[ptr[c]:ptr[c+1]] with the values x beside them and the
+    target target[c]; x and target are libFM's DATA_FLOAT (float32).  num_attr defaults to the
+    largest id + 1 (Data.h:220-222)."""
+
+    def __init__(self, ptr, attr, x, target, num_attr=None):
+        self.ptr = np.ascontiguousarray(ptr, dtype=np.uint64)
+        self.attr = _u32(attr)
+        self.x = np.ascontiguousarray(x, dtype=np.float32)
+        self.target = np.ascontiguousarray(target, dtype=np.float32)
+        if len(self.ptr) != len(self.target) + 1 or len(self.attr) != len(self.x):
+            raise ValueError("ptr / target or attr / x length mismatch")
+        if int(self.ptr[0]) != 0 or int(self.ptr[-1]) != len(self.attr):
+            raise ValueError("ptr must run from 0 to len(attr)")
+        self.num_attr = int(num_attr) if num_attr is not None else (int(self.attr.max()) + 1 if len(self.attr) else 0)
+
+    @property
+    def num_cases(self):
+        return len(self.target)
+
+    @property
+    def rating(self):  # the targets as float64 (what evaluate() compares against)
+        return self.target.astype(np.float64)
+
+    def _c(self):
+        c = _lib.CasesC()
+        c.n, c.nnz, c.num_attr = len(self.target), len(self.attr), self.num_attr
+        c.ptr, c.attr = _ptr(self.ptr, C.c_uint64), _ptr(self.attr, C.c_uint32)
+        c.x, c.target = _ptr(self.x, C.c_float), _ptr(self.target, C.c_float)
+        return c
+
+
+def load_libfm_cases(path):
+    """libFM text with any number of id:value features per line (Data.h:173-283):
+    sbmf_load_libfm_cases.  Entries come back sorted by id within each case."""
+    c = _lib.CasesC()
+    rc = lib.sbmf_load_libfm_cases(str(path).encode(), C.byref(c))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_loader_error().decode())
+    try:
+        n, nnz = int(c.n), int(c.nnz)
+        arr = lambda p, m, t: np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, t)
+        return Cases(arr(c.ptr, n + 1, np.uint64), arr(c.attr, nnz, np.uint32), arr(c.x, nnz, np.float32),
+                     arr(c.target, n, np.float32), num_attr=int(c.num_attr))
+    finally:
+        lib.sbmf_free_cases(C.byref(c))
+
+
+def fm_ranges(train, num_attr=None):
+    """sbmf_fm_ranges: the bounds (uint32, [nranges + 1]) of the fewest contiguous id ranges of
+    [0, num_attr) in which no training case holds two attributes."""
+    p = train.num_attr if num_attr is None else int(num_attr)
+    c, nr = train._c(), C.c_uint32()
+    rc = lib.sbmf_fm_ranges(C.byref(c), p, None, 0, C.byref(nr))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    out = np.zeros(nr.value + 1, dtype=np.uint32)
+    rc = lib.sbmf_fm_ranges(C.byref(c), p, _ptr(out, C.c_uint32), len(out), C.byref(nr))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    return out
 
 
 def _from_ratings(r):
@@ -270,6 +334,16 @@ class FMLearnSBPMF:
     def set_data(self, train, test=None, num_users=0, num_items=0):
         self.init()
         self._train, self._test = train, test
+        if isinstance(train, Cases):  # libFM order / ALS: cases with any number of features
+            if test is not None and not isinstance(test, Cases):
+                raise ValueError("train and test must both be Cases")
+            c = train._c()
+            self._check(lib.sbmf_set_train_cases(self.ctx, C.byref(c)))
+            if test is not None:
+                c = test._c()
+                self._check(lib.sbmf_set_test_cases(self.ctx, C.byref(c)))
+            self._check(lib.sbmf_prepare(self.ctx))
+            return
         self._check(lib.sbmf_set_train(self.ctx, train.num_cases, _ptr(train.user, C.c_uint32),
                                        _ptr(train.item, C.c_uint32), _ptr(train.rating, C.c_double)))
         if test is not None:
@@ -341,6 +415,21 @@ class FMLearnSBPMF:
         bu, bv, b0 = np.zeros(nu), np.zeros(ni), C.c_double()
         self._check(lib.sbmf_get_biases(self.ctx, _ptr(bu, C.c_double), _ptr(bv, C.c_double), C.byref(b0)))
         return bu, bv, b0.value
+
+    def fm_info(self):
+        """The general libFM learner (set_data with Cases, or SBMF_FMM_GENERAL=1): libFM's
+        num_attribute, the ranges of mutually exclusive attributes, and the kernel launches of
+        the last iteration."""
+        a, r, l = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(lib.sbmf_fm_info(self.ctx, C.byref(a), C.byref(r), C.byref(l)))
+        return {"num_attr": a.value, "nranges": r.value, "launches_per_iter": l.value}
+
+    def fm(self):
+        """The general libFM learner's model (w0, w [num_attr], v [K, num_attr])."""
+        p, K = self.fm_info()["num_attr"], self.cfg.num_factor
+        w0, w, v = C.c_double(), np.zeros(p), np.zeros((K, p))
+        self._check(lib.sbmf_get_fm(self.ctx, C.byref(w0), _ptr(w, C.c_double), _ptr(v, C.c_double)))
+        return w0.value, w, v
 
     def timing(self):
         t = _lib.Timing()

@@ -58,6 +58,12 @@ class Ratings(C.Structure):
                 ("rating", C.POINTER(C.c_double))]
 
 
+class CasesC(C.Structure):
+    """sbmf_cases: a libFM data set as a CSR by case."""
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("num_attr", C.c_uint32), ("ptr", C.POINTER(C.c_uint64)),
+                ("attr", C.POINTER(C.c_uint32)), ("x", C.POINTER(C.c_float)), ("target", C.POINTER(C.c_float))]
+
+
 SWEEP_CB = C.CFUNCTYPE(C.c_int, C.POINTER(SweepInfo), C.c_void_p)
 
 _P_U32 = C.POINTER(C.c_uint32)
@@ -126,6 +132,13 @@ SIGNATURES = {
     "sbmf_load_libfm_data": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(Ratings)]),
     "sbmf_save_triples": (C.c_int, [C.c_char_p, C.POINTER(Ratings)]),
     "sbmf_free_ratings": (None, [C.POINTER(Ratings)]),
+    "sbmf_load_libfm_cases": (C.c_int, [C.c_char_p, C.POINTER(CasesC)]),
+    "sbmf_free_cases": (None, [C.POINTER(CasesC)]),
+    "sbmf_fm_ranges": (C.c_int, [C.POINTER(CasesC), C.c_uint32, _P_U32, C.c_uint32, _P_U32]),
+    "sbmf_set_train_cases": (C.c_int, [C.c_void_p, C.POINTER(CasesC)]),
+    "sbmf_set_test_cases": (C.c_int, [C.c_void_p, C.POINTER(CasesC)]),
+    "sbmf_get_fm": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
+    "sbmf_fm_info": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_U32]),
     "sbmf_partition_rows": (C.c_int, [_P_U32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "sbmf_ref_stream": (C.c_int, [C.c_uint32, C.c_int, C.c_double, C.c_uint64, _P_F64]),
     "sbmf_philox_normals": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P_F64]),
