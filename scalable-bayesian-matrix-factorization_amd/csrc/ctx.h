@@ -23,6 +23,7 @@
 #include <rccl/rccl.h>
 #include "kernels.h"
 #include "rng.h"
+#include "fmc.h"
 #include "fmm.h"
 #include "fmg.h"
 #include "foldin.h"
@@ -254,10 +255,11 @@ struct sbmf_ctx {
     // end (once guests.count > 0)
     hipEvent_t fev[3] = {};
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
-    FMLearner* fm = nullptr;  // -method mcmc --order libfm / als (fmm.cpp)
-    // the same chain on cases with any number of features (fmg.cpp): the host copies of
-    // sbmf_set_train_cases / sbmf_set_test_cases (or, with SBMF_FMM_GENERAL=1, the triples of
-    // sbmf_set_train restated as cases: fg_triples, the model then reads back by user / item)
+    // -method mcmc --order libfm / als: libFM's chain (fmc.cpp) on triples (fmm.cpp) or on cases
+    // with any number of features (fmg.cpp).  ctr / cte: the host copies of sbmf_set_train_cases /
+    // sbmf_set_test_cases (or, with SBMF_FMM_GENERAL=1, the triples of sbmf_set_train restated
+    // as cases; the model then still reads back by user / item)
+    FMChain* fm = nullptr;
     struct HostCases {
         std::vector<uint64_t> ptr;
         std::vector<uint32_t> attr;
@@ -276,8 +278,6 @@ struct sbmf_ctx {
             return c;
         }
     } ctr, cte;
-    FGLearner* fg = nullptr;
-    bool fg_triples = false;
     ~sbmf_ctx();
 };
 

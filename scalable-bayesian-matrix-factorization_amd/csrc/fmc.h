@@ -1,0 +1,117 @@
+// fmc.h -- the host side of libFM's MCMC / ALS chain (fm_learn_mcmc.h:411-623 draw_all,
+// fm_learn_mcmc_simultaneous.h:96-245), written once for the two data layouts: the
+// two-attribute learner (fmm.cpp: one user and one item per case, several ranks) and the
+// general one (fmg.cpp: cases with any number of features, exact by ranges).
+//
+// Per iteration, in libFM's order:
+//   1. alpha ~ Gamma((alpha_0 + N)/2, (gamma_0 + sum e^2)/2)          (device sums, host draw)
+//   2. w0 ~ N(...), e -= w0_old - w0                                    (device sum, host draw)
+//   3. w group hyperparameters (host, sums on the device), then every w (the layout's pass)
+//   4. v group hyperparameters of every factor (host), then per factor f every v[f][.]
+//   5. re-predict train and test, running-mean test RMSE
+// Reference RNG mode replays the reference's glibc rand() stream draw for draw (rng.h): the
+// host draws the scalars in consumption order and fills the one normal per attribute of the w
+// and v passes ahead of the launches.  Philox mode fills those normals on the device.  ALS
+// (do_sample = do_multilevel = 0) draws nothing: alpha = 1, the draws take their posterior means.
+//
+// FMChain owns the model, the hyperparameter state, the generator and every buffer the two
+// layouts share; a learner derives from it and supplies what depends on how the cases are
+// stored, through the hooks below.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/sbmf.h"
+#include "common.h"
+#include "rng.h"
+
+namespace sbmf {
+
+struct FMChain {
+    sbmf_config cfg{};
+    uint32_t K = 0, Kp = 0, p = 0;  // p: libFM's num_attribute
+    uint64_t N = 0, T = 0;          // train cases (all ranks), test cases
+    int k0 = 1, k1 = 1, do_sample = 1, do_multilevel = 1;
+    double lo = 1.0, hi = 5.0;  // the train target range (min/max_target)
+    double alpha = 1.0, w0 = 0.0, w_mu = 0.0, w_lambda = 0.0;
+    std::vector<double> v_mu, v_lambda;
+    uint32_t it = 0, n_launch = 0;
+    uint32_t nranges = 0;   // the general learner's ranges (the two-attribute learner has none: 0)
+    uint32_t I = 0, J = 0;  // users-first layout (user u -> attribute u, item i -> I + i); I = 0: cases, no such view
+    GlibcRand grand{1};
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {};
+    DBuf d_w, d_v, d_vT, d_zw, d_zv, d_pthis, d_sum, d_part, d_tpart, d_res, d_scratch;
+    // the hyperparameter draws' sums (k_fmm_hsums): per v column f and for w (index K),
+    // {mu, gm's initial value} in, {gm, m} out
+    DBuf d_hmg, d_hsum;
+    std::vector<double> h_mg, h_hs;
+
+    virtual ~FMChain();
+
+    // ---- what a learner supplies.  A hook counts its own launches in n_launch unless said otherwise.
+    // {sum e^2, sum (e - w0)} over every rank's residuals into s, valid after the next wait on
+    // the stream; d_res[0..1] is the hook's to use (the chain counts two launches)
+    virtual void residual_sums(double* s) = 0;
+    // e -= d over this rank's cases (the chain counts the launch)
+    virtual void shift_residuals(double d) = 0;
+    virtual void start_passes() {}  // before the w pass
+    virtual void w_pass() = 0;      // draw_w (:670-719) of every attribute, normals d_zw[a]
+    virtual void v_pass(uint32_t f) = 0;  // draw_v (:780-835) of factor f, normals d_zv[a * K + f]
+    virtual void sync_users() {}    // after the last v pass
+    // predict_data_and_write_to_eterms of the train set from d_vT / d_w: e = prediction - target,
+    // the blocks' squared errors to d_part (the chain counts the launch) ...
+    virtual void predict_train_cases() = 0;
+    // ... their sum to `out` (device), and what the other ranks add to it (h, after the wait)
+    virtual void train_sum(double* out) = 0;
+    virtual void gather_train_sum(double* h) {}
+    // the test set: d_pthis, d_sum and d_tpart as fmm_predict_test writes them (the chain counts the launch)
+    virtual void predict_test(double it1) = 0;
+
+    // ---- what the chain does
+    // the shared set-up, last in a learner's create (its data uploaded): the flags, the target
+    // range of the train targets y[N], the buffers (nl: this rank's train cases), the initial
+    // model in either RNG mode and the starting predictions
+    void setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr, uint64_t n, uint64_t nl, uint64_t nt,
+               const float* y);
+    void predict_train();
+    void run(uint32_t iters, sbmf_sweep_cb cb, void* user);
+    void predict_out(double* out);                 // the -out predictions
+    void hyper_out(double* h4k, double* alpha_out);  // [v_lambda | v_mu | w_lambda,w_mu,0.. | 0]
+    void model(double* w0_out, double* w, double* v);  // w[p], v[K][p]
+    // the users-first layout read by user and item: v as [I][K] and [J][K], w as [I] and [J]
+    // (rows at or past p read 0), w0; refused when the learner was given cases (I = 0)
+    void factors(double* U, double* V);
+    void biases(double* bu, double* bv, double* b0);
+
+private:
+    template <class G>
+    void init_model(G& g, std::vector<double>& h_w, std::vector<double>& h_v);
+    template <class G>
+    void draw_hyper_w(G& g);
+    template <class G>
+    void draw_hyper_v(G& g);
+    template <class G>
+    void fill_normals(G& g, DBuf& d, uint32_t cols, uint32_t tag);
+    template <class G>
+    void sweep_draws(G& g);
+};
+
+// ---- rows by length, for both learners' pass launches
+// SBMF_FMM_LONG moves the long-row bound (default 4096, at least 256), SBMF_FMM_CHUNK the chunk
+// size (default 4096: the 1024-thread workgroup's four cases per thread; 0 turns chunks off)
+void fm_long_bounds(uint32_t& longb, uint32_t& chunk);
+static const int fm_bin_tpr[3] = {64, 256, 1024};  // threads per row of bin 0, 1, 2
+// rows [r0, r1) of ptr binned by length: <= 256 entries bin 0, <= longb bin 1, longer bin 2; the
+// longest first within a bin: blocks start roughly in index order, so a long row dispatched
+// late would set the launch's tail (rows are independent: the order changes no result)
+void fm_bin_rows(const std::vector<uint32_t>& ptr, uint32_t r0, uint32_t r1, uint32_t longb, std::vector<uint32_t> b[3]);
+// rows[0..nrows) cut into chunks of at most `chunk` entries {row, first entry, entries, i},
+// a row's chunks consecutive, appended to chunks; cfirst gets nrows + 1 chunk offsets relative
+// to the first chunk appended
+void fm_cut_chunks(const std::vector<uint32_t>& ptr, const uint32_t* rows, uint32_t nrows, uint32_t chunk,
+                   std::vector<uint4>& chunks, std::vector<uint32_t>& cfirst);
+
+}  // namespace sbmf

@@ -78,17 +78,9 @@ hipError_t fmg_predict_train(const FGPredictArgs& a, double2* eq, double* part, 
 hipError_t fmg_predict_test(const FGPredictArgs& a, double it1, double* pthis, double* sum_all, double* part,
                             hipStream_t st);
 
-// ---- host learner (fmg.cpp), driven by the C ABI in sbmf.cpp
-struct FGLearner;
-FGLearner* fmg_create(const sbmf_config& c, const sbmf_cases& train, const sbmf_cases& test, hipStream_t st);
-void fmg_destroy(FGLearner* L);
-void fmg_run(FGLearner* L, uint32_t iters, sbmf_sweep_cb cb, void* user);
-void fmg_predict_out(FGLearner* L, double* out);
-void fmg_model(FGLearner* L, double* w0, double* w, double* v);  // w[p], v[K][p]
-void fmg_hyper_out(FGLearner* L, double* h4k, double* alpha);    // as fmm_hyper_out
-uint32_t fmg_launches(const FGLearner* L);
-uint32_t fmg_num_attribute(const FGLearner* L);
-uint32_t fmg_num_ranges(const FGLearner* L);
+// ---- host learner (fmg.cpp): libFM's chain (FMChain, fmc.h) on this layout, driven by the C ABI in sbmf.cpp
+struct FMChain;
+FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& train, const sbmf_cases& test, hipStream_t st);
 // the ranges of sbmf_fm_ranges over [0, p) (train cases; ids >= train.num_attr have no case)
 void fm_ranges(const sbmf_cases& train, uint32_t p, std::vector<uint32_t>& bounds);
 

@@ -106,22 +106,14 @@ hipError_t fmm_predict_train(const FMPredictArgs& a, const uint32_t* own_u, cons
 hipError_t fmm_predict_test(const FMPredictArgs& a, const uint32_t* su, const uint32_t* si, const float* y,
                             uint64_t n, double it1, double* pthis, double* sum_all, double* part, hipStream_t st);
 
-// ---- host learner (fmm.cpp), driven by the C ABI in sbmf.cpp
-struct FMLearner;
+// ---- host learner (fmm.cpp): libFM's chain (FMChain, fmc.h) on this layout, driven by the C ABI in sbmf.cpp
+struct FMChain;
 class Comm;
 // comm: null, or R > 1 ranks (one process per GPU): users split by
 // sbmf_partition_rows, every case local to its user's rank, item rows summed
 // over the ranks (as the online VB learner, vbo.cpp)
-FMLearner* fmm_create(const sbmf_config& c, uint64_t n, const uint32_t* u, const uint32_t* i, const double* r,
-                      uint64_t nt, const uint32_t* tu, const uint32_t* ti, const double* tr, uint32_t I, uint32_t J,
-                      hipStream_t st, Comm* comm = nullptr);
-void fmm_destroy(FMLearner* L);
-void fmm_run(FMLearner* L, uint32_t iters, sbmf_sweep_cb cb, void* user);
-void fmm_predict_out(FMLearner* L, double* out);       // the -out predictions (fm_learn_mcmc::predict)
-void fmm_factors(FMLearner* L, double* U, double* V);  // v of the users [I][K] and items [J][K]
-void fmm_biases(FMLearner* L, double* bu, double* bv, double* b0);  // w of users, items; w0
-void fmm_hyper_out(FMLearner* L, double* h4k, double* alpha);       // [v_lambda | v_mu | w_lambda,w_mu,0.. | 0]
-uint32_t fmm_launches(const FMLearner* L);
-uint32_t fmm_num_attribute(const FMLearner* L);
+FMChain* fmm_create(const sbmf_config& c, uint64_t n, const uint32_t* u, const uint32_t* i, const double* r,
+                    uint64_t nt, const uint32_t* tu, const uint32_t* ti, const double* tr, uint32_t I, uint32_t J,
+                    hipStream_t st, Comm* comm = nullptr);
 
 }  // namespace sbmf

@@ -33,8 +33,7 @@ Audit& audit() {
 // ===================================================================== C ABI
 sbmf_ctx::~sbmf_ctx() {
     vbo_destroy(vb);
-    fmm_destroy(fm);
-    fmg_destroy(fg);
+    delete fm;
     using namespace sbmf;
     pinned_free(h_pinned, h_pinned_bytes);
     pinned_free(h_pre, h_pre_bytes);
@@ -314,12 +313,16 @@ static bool libfm_method(const sbmf_ctx* c) {
 }
 
 // The general learner (fmg.cpp) on the cases given so far: one rank only
-static void prepare_cases(sbmf_ctx* c) {
+static void prepare_cases(sbmf_ctx* c, bool triples) {
     if (c->nranks > 1 || c->virt || c->comm != &c->own_comm || c->own_comm.active())
         sbmf::fail(SBMF_E_STATE, "the general libFM learner (cases with any number of features) runs on one rank: "
                                  "this context joined a communicator or is a virtual rank");
     c->K = c->cfg.num_factor;
-    c->fg = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st);
+    c->fm = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st);
+    if (triples) {  // the users-first layout: the model reads back by user / item
+        c->fm->I = c->I;
+        c->fm->J = c->J;
+    }
     c->prepared = true;
 }
 
@@ -347,7 +350,7 @@ static void triples_to_cases(const std::vector<uint32_t>& u, const std::vector<u
 
 static void prepare_ctx(sbmf_ctx* c) {
     if (c->ctr.set) {
-        prepare_cases(c);
+        prepare_cases(c, false);
         return;
     }
     if (c->cte.set) sbmf::fail(SBMF_E_STATE, "sbmf_set_test_cases without sbmf_set_train_cases");
@@ -373,8 +376,7 @@ static void prepare_ctx(sbmf_ctx* c) {
     if (libfm_method(c) && gen && std::atoi(gen) != 0) {
         triples_to_cases(c->tu, c->ti, c->tr, c->I, c->ctr);
         triples_to_cases(c->su, c->si, c->sr, c->I, c->cte);
-        c->fg_triples = true;
-        prepare_cases(c);
+        prepare_cases(c, true);
         return;
     }
     if (c->cfg.method == SBMF_METHOD_VB)
@@ -483,9 +485,10 @@ int sbmf_get_fm(sbmf_ctx* ctx, double* w0, double* w, double* v) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
-    if (!ctx->fg) sbmf::fail(SBMF_E_STATE, "sbmf_get_fm: this context does not run the general libFM learner");
+    if (!ctx->fm || !ctx->fm->nranges)
+        sbmf::fail(SBMF_E_STATE, "sbmf_get_fm: this context does not run the general libFM learner");
     HIPCHK(hipSetDevice(ctx->cfg.device));
-    fmg_model(ctx->fg, w0, w, v);
+    ctx->fm->model(w0, w, v);
     API_END(ctx)
 }
 
@@ -493,10 +496,11 @@ int sbmf_fm_info(sbmf_ctx* ctx, uint32_t* num_attr, uint32_t* nranges, uint32_t*
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
-    if (!ctx->fg) sbmf::fail(SBMF_E_STATE, "sbmf_fm_info: this context does not run the general libFM learner");
-    if (num_attr) *num_attr = fmg_num_attribute(ctx->fg);
-    if (nranges) *nranges = fmg_num_ranges(ctx->fg);
-    if (launches_per_iter) *launches_per_iter = fmg_launches(ctx->fg);
+    if (!ctx->fm || !ctx->fm->nranges)
+        sbmf::fail(SBMF_E_STATE, "sbmf_fm_info: this context does not run the general libFM learner");
+    if (num_attr) *num_attr = ctx->fm->p;
+    if (nranges) *nranges = ctx->fm->nranges;
+    if (launches_per_iter) *launches_per_iter = ctx->fm->n_launch;
     API_END(ctx)
 }
 
@@ -554,16 +558,10 @@ int sbmf_run(sbmf_ctx* ctx, uint32_t sweeps, sbmf_sweep_cb cb, void* user) {
         ctx->timing.ms_vb_factor = vbo_factor_ms(ctx->vb);
         return SBMF_OK;
     }
-    if (ctx->fg) {
-        fmg_run(ctx->fg, sweeps, cb, user);
-        ctx->timing = sbmf_timing{};
-        ctx->timing.n_launch = fmg_launches(ctx->fg);
-        return SBMF_OK;
-    }
     if (ctx->fm) {
-        fmm_run(ctx->fm, sweeps, cb, user);
+        ctx->fm->run(sweeps, cb, user);
         ctx->timing = sbmf_timing{};
-        ctx->timing.n_launch = fmm_launches(ctx->fm);
+        ctx->timing.n_launch = ctx->fm->n_launch;
         return SBMF_OK;
     }
     ctx->cfg.precision == SBMF_F32 ? run_sweeps_T<float>(ctx, sweeps, cb, user) : run_sweeps_T<double>(ctx, sweeps, cb, user);
@@ -579,12 +577,8 @@ int sbmf_predict(sbmf_ctx* ctx, double* out) {
         vbo_predict_out(ctx->vb, out);
         return SBMF_OK;
     }
-    if (ctx->fg) {
-        fmg_predict_out(ctx->fg, out);
-        return SBMF_OK;
-    }
     if (ctx->fm) {
-        fmm_predict_out(ctx->fm, out);
+        ctx->fm->predict_out(out);
         return SBMF_OK;
     }
     const uint64_t T_ = ctx->su.size();
@@ -607,23 +601,8 @@ int sbmf_get_factors(sbmf_ctx* ctx, double* U, double* V) {
         vbo_factors(ctx->vb, U, V);
         return SBMF_OK;
     }
-    if (ctx->fg) {
-        if (!ctx->fg_triples)
-            sbmf::fail(SBMF_E_STATE, "a context given cases has no user / item tables: read the model with sbmf_get_fm");
-        // SBMF_FMM_GENERAL: v of the users [I][K] and items [J][K]; items past the attribute count read 0
-        const uint32_t p = fmg_num_attribute(ctx->fg), K = ctx->K, I = ctx->I;
-        std::vector<double> h((size_t)K * p);
-        fmg_model(ctx->fg, nullptr, nullptr, h.data());
-        for (uint32_t f = 0; f < K; ++f) {
-            if (U)
-                for (uint32_t a = 0; a < I; ++a) U[(size_t)a * K + f] = h[(size_t)f * p + a];
-            if (V)
-                for (uint32_t a = 0; a < ctx->J; ++a) V[(size_t)a * K + f] = I + a < p ? h[(size_t)f * p + I + a] : 0.0;
-        }
-        return SBMF_OK;
-    }
-    if (ctx->fm) {
-        fmm_factors(ctx->fm, U, V);
+    if (ctx->fm) {  // libFM's v of the users [I][K] and items [J][K]
+        ctx->fm->factors(U, V);
         return SBMF_OK;
     }
     if (U) sbmf::download_table(ctx, ctx->d_U, U, ctx->I);
@@ -635,7 +614,7 @@ int sbmf_set_factors(sbmf_ctx* ctx, const double* U, const double* V) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
-    if (ctx->vb || ctx->fm || ctx->fg)
+    if (ctx->vb || ctx->fm)
         sbmf::fail(SBMF_E_STATE, "sbmf_set_factors is not supported by the VB / libFM learners");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->st));
@@ -654,12 +633,8 @@ int sbmf_get_hyper(sbmf_ctx* ctx, double* h, double* tau) {
         vbo_hyper_out(ctx->vb, h, tau);
         return SBMF_OK;
     }
-    if (ctx->fg) {
-        fmg_hyper_out(ctx->fg, h, tau);
-        return SBMF_OK;
-    }
     if (ctx->fm) {
-        fmm_hyper_out(ctx->fm, h, tau);
+        ctx->fm->hyper_out(h, tau);
         return SBMF_OK;
     }
     const uint32_t K = ctx->K;
@@ -683,19 +658,8 @@ int sbmf_get_biases(sbmf_ctx* ctx, double* bu, double* bv, double* b0) {
         vbo_biases(ctx->vb, bu, bv, b0);
         return SBMF_OK;
     }
-    if (ctx->fg) {
-        if (!ctx->fg_triples)
-            sbmf::fail(SBMF_E_STATE, "a context given cases has no user / item biases: read the model with sbmf_get_fm");
-        const uint32_t p = fmg_num_attribute(ctx->fg), I = ctx->I;
-        std::vector<double> h(p);
-        fmg_model(ctx->fg, b0, h.data(), nullptr);
-        if (bu) std::copy(h.begin(), h.begin() + I, bu);
-        if (bv)
-            for (uint32_t a = 0; a < ctx->J; ++a) bv[a] = I + a < p ? h[I + a] : 0.0;
-        return SBMF_OK;
-    }
     if (ctx->fm) {  // libFM's w (users, items) and w0
-        fmm_biases(ctx->fm, bu, bv, b0);
+        ctx->fm->biases(bu, bv, b0);
         return SBMF_OK;
     }
     if (!ctx->bias) sbmf::fail(SBMF_E_STATE, "not a biased sampler (quirks bias2 / bias22) or the VB learner");
@@ -711,7 +675,7 @@ int sbmf_get_dims(sbmf_ctx* ctx, uint32_t* nu, uint32_t* ni, uint64_t* ntr, uint
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     if (nu) *nu = ctx->I;
     if (ni) *ni = ctx->J;
-    const bool cases = ctx->ctr.set && !ctx->fg_triples;  // given as cases: no user / item dims
+    const bool cases = ctx->ctr.set && ctx->tu.empty();  // given as cases (never beside triples): no user / item dims
     if (ntr) *ntr = cases ? ctx->ctr.y.size() : ctx->tu.size();
     if (nte) *nte = cases ? ctx->cte.y.size() : ctx->su.size();
     API_END(ctx)

@@ -134,6 +134,28 @@ def small_cases():
     return Cases(*parse_text(SMALL_TEXT)), Cases(*parse_text(SMALL_TEST_TEXT))
 
 
+EDGE_LENGTHS = [0, 1, 63, 64, 65, 255, 256, 257, 1025]
+
+
+def edge_set():
+    """A one-hot field whose nine attributes have exactly the EDGE_LENGTHS cases (the one-wave bin's
+    end, the chunk size, the long-row bound, each +-1, and a row of 17 chunks), a 13-valued
+    one-hot field with real values beside it, and a two-valued multi-hot field."""
+    own = np.repeat(np.arange(len(EDGE_LENGTHS)), EDGE_LENGTHS)
+    n = len(own)
+    own = own[(np.arange(n) * 7919) % n]  # 7919 is prime to n = 1986: a permutation
+    rows = []
+    for c in range(n):
+        f = [(int(own[c]), 1.0), (9 + c % 13, 0.5 + 0.25 * (c % 4))]
+        if c % 3 == 0:
+            f.append((22, 0.5))
+        if c % 5 < 2:
+            f.append((23, -0.75 if c % 7 == 0 else 1.0))
+        rows.append((1.0 + (c * 7) % 5, f))
+    test = [(1.0 + (c * 3) % 5, [(int(own[c * 17 % n]), 1.0), (9 + c % 13, 1.25), (24, 1.0)]) for c in range(64)]
+    return rows_to_cases(rows), rows_to_cases(test)
+
+
 # ---- libFM's ALS, restated serially in numpy (fm_learn_mcmc.h with do_sample = do_multilevel = 0):
 # draw_w0 (:627-668), draw_w (:670-719), add_main_q (:384-409), draw_v (:780-835) and
 # predict_data_and_write_to_eterms (:117-348), attribute by attribute in ascending order, in

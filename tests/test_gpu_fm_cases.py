@@ -221,32 +221,10 @@ def test_chunked_long_rows_agree_with_unchunked(method, ml100k, monkeypatch):
     B.close()
 
 
-EDGE_LENGTHS = [0, 1, 63, 64, 65, 255, 256, 257, 1025]
-
-
-def _edge_set():
-    """A one-hot field whose nine attributes have exactly the EDGE_LENGTHS cases (the one-wave bin's
-    end, the chunk size, the long-row bound, each +-1, and a row of 17 chunks), a 13-valued
-    one-hot field with real values beside it, and a two-valued multi-hot field."""
-    own = np.repeat(np.arange(len(EDGE_LENGTHS)), EDGE_LENGTHS)
-    n = len(own)
-    own = own[(np.arange(n) * 7919) % n]  # 7919 is prime to n = 1986: a permutation
-    rows = []
-    for c in range(n):
-        f = [(int(own[c]), 1.0), (9 + c % 13, 0.5 + 0.25 * (c % 4))]
-        if c % 3 == 0:
-            f.append((22, 0.5))
-        if c % 5 < 2:
-            f.append((23, -0.75 if c % 7 == 0 else 1.0))
-        rows.append((1.0 + (c * 7) % 5, f))
-    test = [(1.0 + (c * 3) % 5, [(int(own[c * 17 % n]), 1.0), (9 + c % 13, 1.25), (24, 1.0)]) for c in range(64)]
-    return fm_cases.rows_to_cases(rows), fm_cases.rows_to_cases(test)
-
-
 def test_row_lengths_at_every_edge_match_restatement(monkeypatch):
     assert gpu_available()
-    tr, te = _edge_set()
-    assert sorted(np.bincount(tr.attr, minlength=9)[:9].tolist()) == sorted(EDGE_LENGTHS)
+    tr, te = fm_cases.edge_set()
+    assert sorted(np.bincount(tr.attr, minlength=9)[:9].tolist()) == sorted(fm_cases.EDGE_LENGTHS)
     a, b = _restated("edge", tr, te, 4, 2, (0.5, 1.0, 4.0), (1, 2, 5))
     monkeypatch.setenv("SBMF_FMM_LONG", "256")
     monkeypatch.setenv("SBMF_FMM_CHUNK", "64")

@@ -72,6 +72,11 @@ def main():
     if method in ("vb", "libfm", "als"):
         extra["pred"] = L.predict()
         extra["rmse_train"] = np.array([h["rmse_train"] for h in L.history])
+    if method in ("libfm", "als"):  # what tests/test_gpu_fm_pins.py pins beside the above
+        hy = L.hyper()
+        extra["rmse_this"] = np.array([h["rmse_this"] for h in L.history])
+        extra["hyper"] = np.concatenate([hy["sigma_u"], hy["mu_u"], hy["sigma_v"], hy["mu_v"], [hy["tau"]]])
+        extra["n_launch"] = np.array([L.timing().n_launch])
     np.savez(out, U=U, V=V, rmse=L.rmse_trajectory, tau=np.array([h["tau"] for h in L.history]), **extra)
     L.close()
 
