@@ -249,7 +249,10 @@ int sbmf_predict(sbmf_ctx* ctx, double* out);
 int sbmf_get_factors(sbmf_ctx* ctx, double* U, double* V);
 /* Overwrite the factors (row-major doubles).  For checkpoints and tests. */
 int sbmf_set_factors(sbmf_ctx* ctx, const double* U, const double* V);
-/* Hyperparameters [sigma_u | mu_u | sigma_v | mu_v] (4K doubles) and tau. */
+/* Hyperparameters [sigma_u | mu_u | sigma_v | mu_v] (4K doubles) and tau.  On a
+ * libFM MCMC / ALS context with more than one attribute group (sbmf_set_attr_groups)
+ * hyper4k is SBMF_E_STATE -- read sbmf_get_fm_groups --; with hyper4k NULL tau is
+ * still returned. */
 int sbmf_get_hyper(sbmf_ctx* ctx, double* hyper4k, double* tau);
 int sbmf_get_dims(sbmf_ctx* ctx, uint32_t* num_users, uint32_t* num_items, uint64_t* n_train, uint64_t* n_test);
 /* Biased sampler only: b_i [num_users], b_j [num_items] and the global b_0
@@ -542,6 +545,43 @@ int sbmf_get_fm(sbmf_ctx* ctx, double* w0, double* w, double* v);
  * on a context that does not run the general learner. */
 int sbmf_fm_info(sbmf_ctx* ctx, uint32_t* num_attr, uint32_t* nranges, uint32_t* launches_per_iter);
 
+/* --- libFM's attribute groups (bin/libFM -meta) -------------------------------------------- */
+/* libFM's MCMC / ALS learner draws its hyperparameters per attribute group
+ * (fm_learn_mcmc.h:931-1089 loop over meta->num_attr_groups): w_mu[g], w_lambda[g],
+ * v_mu[g][f], v_lambda[g][f], and draw_w / draw_v of attribute a take its group's
+ * (:445-455, :565-577).  group[a] is the group of attribute a for every a <
+ * num_attribute = the largest attribute id over train and test + 2 (libFM counts a
+ * trailing attribute, libfm.cpp:328; for triples the ids are user u -> u, item i ->
+ * num_users + i; sbmf_fm_info reports the number after sbmf_prepare); G = the
+ * largest group id + 1.  A group id no attribute carries is a group of 0 attributes:
+ * its hyperparameters are still drawn (and consume variates), as in libFM.  Groups
+ * need not be contiguous.  Call before sbmf_prepare on a SBMF_METHOD_LIBFM_MCMC /
+ * SBMF_METHOD_ALS context; n != num_attribute is SBMF_E_ARG naming both (here when
+ * the data is already set, else at sbmf_prepare); n = 0 drops the groups; another
+ * method, a context that joined a communicator or a virtual rank is SBMF_E_STATE
+ * naming the reason.  One group (all zeros) is the ungrouped chain, bit for bit.
+ * A triples context (sbmf_set_train) given groups runs through the general learner
+ * (the route of SBMF_FMM_GENERAL=1): the two-attribute kernels keep one group. */
+int sbmf_set_attr_groups(sbmf_ctx* ctx, uint32_t n, const uint32_t* group);
+/* -regular with 1 + 2G values (libfm.cpp:514-521): the groups' fixed (ALS) or starting
+ * (MCMC) precisions regw[g] of w and regv[g] of every v[.][f]; cfg.reg0 stays w0's.
+ * Without it every group takes cfg.regw / cfg.regv.  G must match the groups set by
+ * sbmf_set_attr_groups (checked here when they are set, else at sbmf_prepare):
+ * SBMF_E_ARG.  G = 0 drops the values.  State errors as sbmf_set_attr_groups. */
+int sbmf_set_group_regular(sbmf_ctx* ctx, uint32_t G, const double* regw, const double* regv);
+/* The groups and their hyperparameters after sbmf_prepare: *G, cnt[G] (attributes
+ * per group, over all num_attribute ids), w_lambda[G], w_mu[G], v_lambda[G][K],
+ * v_mu[G][K].  Any pointer may be NULL; works for one group too.  sbmf_get_hyper on a
+ * context with G > 1 is SBMF_E_STATE and points here. */
+int sbmf_get_fm_groups(sbmf_ctx* ctx, uint32_t* G, uint32_t* cnt, double* w_lambda, double* w_mu, double* v_lambda,
+                       double* v_mu);
+/* A -meta file (DataMetaInfo::loadGroupsFromFile, Data.h:49-61): the first num_attr
+ * whitespace-separated unsigned integers into group[], *G = the largest + 1.  A file
+ * with fewer entries, or an entry that is no unsigned integer, is SBMF_E_IO naming
+ * the entry (sbmf_loader_error) -- the reference reads past the end there; entries
+ * after the first num_attr are ignored.  Host only. */
+int sbmf_load_libfm_meta(const char* path, uint32_t num_attr, uint32_t* group, uint32_t* G);
+
 /* --- multi-GPU layout (host only) ---------------------------------------------------------- */
 /* The row partition every rank uses: contiguous row blocks balanced by
  * ratings (ptr = CSR/CSC offsets [R+1]), boundaries rounded to 256 rows.
@@ -617,6 +657,11 @@ typedef struct sbmf_device_usage {
     int64_t streams, events, contexts, comms;
 } sbmf_device_usage;
 int sbmf_test_device_usage(int device, sbmf_device_usage* out);
+/* The grouped column-sums kernel (k_fmg_gsums) on the general learner's current
+ * model and current mu: out[(c * G + g) * 2 + {0: gm, 1: m}] for the columns c = 0 ..
+ * K (v column c, then w) and the groups g, as the next iteration's hyperparameter
+ * draws would read them. */
+int sbmf_test_fm_group_sums(sbmf_ctx* ctx, double* out);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,11 @@ Four settings, in alternating runs (--reps of each):
   (b) the same cases through the general learner (SBMF_FMM_GENERAL=1): the price of generality,
   (c) the cases with a 7-value and a 24-value one-hot field added ((u + 3 i) mod 7, (5 u + i) mod 24),
   (d) the same with a 5-tag multi-hot field (tag t present when bit t of the item id is set).
+A setting followed by a digit runs the same cases with that many attribute groups (libFM's
+-meta, set_groups): b2 = users | items through the general learner, c2 / d2 = users | everything
+else, c4 = users | items | the 7-value field | the 24-value field with the trailing attribute,
+d4 = users | items | the two one-hot fields | the tags.  (a has no grouped form: the
+two-attribute kernels keep one group.)
 Per run: ms per iteration from a host clock around --steps iterations ending in a device
 synchronise, after --warmup iterations, and the mean of the iterations' HIP-event times
 (sweep + evaluation); launches per iteration and the ranges from fm_info.  One JSON line on
@@ -72,6 +77,24 @@ def main():
     I, J = int(dims[0]), int(dims[1])
     sets = {}
 
+    def groups(setting, p):
+        """The group table of a grouped setting (None for a plain one)."""
+        if len(setting) == 1:
+            return None
+        n = int(setting[1:])
+        g = np.zeros(p, np.uint32)
+        if setting[0] == "b":  # triples: the attributes are user u -> u, item i -> (largest user id + 1) + i
+            g[int(max(train[0].max(), test[0].max())) + 1:] = 1
+        elif n == 2:
+            g[I:] = 1
+        elif n == 4 and setting[0] in "cd":
+            g[I:I + J] = 1
+            g[I + J:] = 2
+            g[I + J + (7 if setting[0] == "c" else 31):] = 3
+        else:
+            raise SystemExit("no %d-group form of setting %s" % (n, setting[0]))
+        return g
+
     def data(setting):
         if setting not in sets:
             if setting in "ab":
@@ -81,12 +104,16 @@ def main():
                 sets[setting] = tuple(build_cases(d[0], d[1], d[2], I, J, f) for d in (train, test))
         return sets[setting]
 
-    def run(setting):
+    def run(name):
+        setting = name[0]
         tr, te = data(setting)
-        if setting == "b":
+        if name == "b":
             os.environ["SBMF_FMM_GENERAL"] = "1"
         try:
             L = FMLearnSBPMF(num_factor=args.K, seed=2015, rng="philox", method="mcmc", order="libfm", init_stdev=0.1)
+            if len(name) > 1:
+                L.set_groups(groups(name, int(max(train[0].max(), test[0].max())) + int(max(train[1].max(), test[1].max())) + 3
+                                    if setting == "b" else max(tr.num_attr, te.num_attr) + 1))
             L.set_data(tr, te)
         finally:
             os.environ.pop("SBMF_FMM_GENERAL", None)
@@ -103,8 +130,10 @@ def main():
             info = L.fm_info()
             res.update(num_attr=info["num_attr"], nranges=info["nranges"])
             res["nnz"] = 2 * tr.num_cases if setting == "b" else int(len(tr.attr))
+        if len(name) > 1:
+            res["groups"] = L.fm_groups()["cnt"].tolist()
         L.close()
-        print("# %s %s" % (setting, json.dumps(res)), flush=True)
+        print("# %s %s" % (name, json.dumps(res)), flush=True)
         return res
 
     names = [s for s in args.settings.split(",") if s]

@@ -260,6 +260,7 @@ struct sbmf_ctx {
     // sbmf_set_test_cases (or, with SBMF_FMM_GENERAL=1, the triples of sbmf_set_train restated
     // as cases; the model then still reads back by user / item)
     FMChain* fm = nullptr;
+    FMGroups fmgroups;  // sbmf_set_attr_groups / sbmf_set_group_regular, read at sbmf_prepare
     struct HostCases {
         std::vector<uint64_t> ptr;
         std::vector<uint32_t> attr;

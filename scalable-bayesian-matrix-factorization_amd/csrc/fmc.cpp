@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "fmg.h"
 #include "fmm.h"
 #include "kernels.h"
 
@@ -18,15 +19,15 @@ FMChain::~FMChain() {
     for (auto& e : ev) event_destroy(e);
 }
 
-template <class G>
-static double gaussian(G& g, double mean, double stdev) {  // random.h:166-172
+template <class R>
+static double gaussian(R& g, double mean, double stdev) {  // random.h:166-172
     if (stdev == 0.0 || std::isnan(stdev)) return mean;
     return mean + stdev * leva_normal(g);
 }
 
 // fm_model::init (fm_model.h:87-96: v, f-major) then w (libfm.cpp:412)
-template <class G>
-void FMChain::init_model(G& g, std::vector<double>& h_w, std::vector<double>& h_v) {
+template <class R>
+void FMChain::init_model(R& g, std::vector<double>& h_w, std::vector<double>& h_v) {
     const double sd = cfg.init_stdev >= 0 ? cfg.init_stdev : 0.1;
     h_v.resize((size_t)K * p);
     h_w.resize(p);
@@ -34,63 +35,152 @@ void FMChain::init_model(G& g, std::vector<double>& h_w, std::vector<double>& h_
     for (double& x : h_w) x = gaussian(g, 0.0, sd);
 }
 
-// fm_learn_mcmc.h:951-1009 (one group: every attribute).  gm = beta_0 (w_mu - mu_0)^2 + gamma_0 +
-// sum_i (w_i - w_mu)^2 and m = sum_i w_i come from the device, summed in the reference's order
-template <class G>
-void FMChain::draw_hyper_w(G& g) {
+// fm_learn_mcmc.h:931-1007: draw_w_lambda over every group, then draw_w_mu over every group.  Per
+// group g with cnt[g] attributes: gm = beta_0 (w_mu[g] - mu_0)^2 + gamma_0 + sum_{i in g} (w_i -
+// w_mu[g])^2 and m = sum_{i in g} w_i come from the device, each summed over the group's
+// attributes in ascending id, the order the reference's one loop over all attributes gives every
+// group.  A NaN / inf draw restores the value and ends that function (the reference returns): the
+// groups after it keep their values and consume no variate.
+template <class R>
+void FMChain::draw_hyper_w(R& g) {
     const double alpha_0 = 1.0, beta_0 = 1.0, mu_0 = 0.0;
     if (!do_multilevel) {
-        w_mu = mu_0;
+        std::fill(w_mu.begin(), w_mu.end(), mu_0);
         return;
     }
-    const double gm = h_hs[2 * K];
-    const double a = alpha_0 + p + 1;
-    const double old = w_lambda;
-    w_lambda = do_sample ? mt_gamma(g, a / 2.0) / (gm / 2.0) : a / gm;
-    if (std::isnan(w_lambda) || std::isinf(w_lambda)) w_lambda = old;
-    double m = h_hs[2 * K + 1];
-    m = (m + beta_0 * mu_0) / (p + beta_0);
-    const double s2 = 1.0 / ((p + beta_0) * w_lambda);
-    const double om = w_mu;
-    w_mu = do_sample ? gaussian(g, m, std::sqrt(s2)) : m;
-    if (std::isnan(w_mu) || std::isinf(w_mu)) w_mu = om;
+    const double* hs = h_hs.data() + 2 * (size_t)K * G;
+    for (uint32_t q = 0; q < G; ++q) {
+        const double gm = hs[2 * q];
+        const double a = alpha_0 + cnt[q] + 1;
+        const double old = w_lambda[q];
+        w_lambda[q] = do_sample ? mt_gamma(g, a / 2.0) / (gm / 2.0) : a / gm;
+        if (std::isnan(w_lambda[q]) || std::isinf(w_lambda[q])) {
+            w_lambda[q] = old;
+            break;
+        }
+    }
+    for (uint32_t q = 0; q < G; ++q) {
+        double m = hs[2 * q + 1];
+        m = (m + beta_0 * mu_0) / (cnt[q] + beta_0);
+        const double s2 = 1.0 / ((cnt[q] + beta_0) * w_lambda[q]);
+        const double om = w_mu[q];
+        w_mu[q] = do_sample ? gaussian(g, m, std::sqrt(s2)) : m;
+        if (std::isnan(w_mu[q]) || std::isinf(w_mu[q])) {
+            w_mu[q] = om;
+            break;
+        }
+    }
 }
 
-// fm_learn_mcmc.h:1011-1089 (a NaN / inf ends that draw's factor loop); the sums over each
-// column as for w: gm from beta_0 (mu_f - mu_0)^2 + gamma_0 adding (v_fi - mu_f)^2, m = sum_i v_fi
-template <class G>
-void FMChain::draw_hyper_v(G& g) {
+// fm_learn_mcmc.h:1011-1089: draw_v_lambda for f, for g, then draw_v_mu for f, for g (a NaN / inf
+// ends that function: every later factor and group keeps its value); the sums over each column's
+// groups as for w: gm from beta_0 (mu_gf - mu_0)^2 + gamma_0 adding (v_fi - mu_gf)^2, m = sum v_fi
+template <class R>
+void FMChain::draw_hyper_v(R& g) {
     const double alpha_0 = 1.0, beta_0 = 1.0, mu_0 = 0.0;
     if (!do_multilevel) {
         std::fill(v_mu.begin(), v_mu.end(), mu_0);
         return;
     }
-    for (uint32_t f = 0; f < K; ++f) {
-        const double gm = h_hs[2 * f];
-        const double a = alpha_0 + p + 1;
-        const double old = v_lambda[f];
-        v_lambda[f] = do_sample ? mt_gamma(g, a / 2.0) / (gm / 2.0) : a / gm;
-        if (std::isnan(v_lambda[f]) || std::isinf(v_lambda[f])) {
-            v_lambda[f] = old;
-            break;
+    bool stop = false;
+    for (uint32_t f = 0; f < K && !stop; ++f)
+        for (uint32_t q = 0; q < G; ++q) {
+            double& lam = v_lambda[(size_t)q * K + f];
+            const double gm = h_hs[2 * ((size_t)f * G + q)];
+            const double a = alpha_0 + cnt[q] + 1;
+            const double old = lam;
+            lam = do_sample ? mt_gamma(g, a / 2.0) / (gm / 2.0) : a / gm;
+            if (std::isnan(lam) || std::isinf(lam)) {
+                lam = old;
+                stop = true;
+                break;
+            }
         }
+    stop = false;
+    for (uint32_t f = 0; f < K && !stop; ++f)
+        for (uint32_t q = 0; q < G; ++q) {
+            double& mu = v_mu[(size_t)q * K + f];
+            double m = h_hs[2 * ((size_t)f * G + q) + 1];
+            m = (m + beta_0 * mu_0) / (cnt[q] + beta_0);
+            const double s2 = 1.0 / ((cnt[q] + beta_0) * v_lambda[(size_t)q * K + f]);
+            const double old = mu;
+            mu = do_sample ? gaussian(g, m, std::sqrt(s2)) : m;
+            if (std::isnan(mu) || std::isinf(mu)) {
+                mu = old;
+                stop = true;
+                break;
+            }
+        }
+}
+
+// The groups' member lists for the grouped sums kernel (built once; without a group table one
+// contiguous group of every attribute)
+void FMChain::ensure_group_lists() {
+    if (d_gptr.p) return;
+    std::vector<uint32_t> gptr((size_t)G + 1, 0), gfirst(G, 0xffffffffu), gidx(std::max<uint32_t>(p, 1), 0);
+    for (uint32_t a = 0; a < p; ++a) gptr[(grp.empty() ? 0 : grp[a]) + 1]++;
+    for (uint32_t q = 0; q < G; ++q) gptr[q + 1] += gptr[q];
+    std::vector<uint32_t> fill(gptr.begin(), gptr.end() - 1);
+    for (uint32_t a = 0; a < p; ++a) gidx[fill[grp.empty() ? 0 : grp[a]]++] = a;
+    for (uint32_t q = 0; q < G; ++q) {
+        const uint32_t b = gptr[q], n = gptr[q + 1] - b;
+        if (n == 0 || gidx[b + n - 1] - gidx[b] == n - 1) gfirst[q] = n ? gidx[b] : 0;
     }
-    for (uint32_t f = 0; f < K; ++f) {
-        double m = h_hs[2 * f + 1];
-        m = (m + beta_0 * mu_0) / (p + beta_0);
-        const double s2 = 1.0 / ((p + beta_0) * v_lambda[f]);
-        const double old = v_mu[f];
-        v_mu[f] = do_sample ? gaussian(g, m, std::sqrt(s2)) : m;
-        if (std::isnan(v_mu[f]) || std::isinf(v_mu[f])) {
-            v_mu[f] = old;
-            break;
+    upload(d_gptr, gptr, st);
+    upload(d_gfirst, gfirst, st);
+    upload(d_gidx, gidx, st);
+    HIPCHK(hipStreamSynchronize(st));  // the vectors are locals
+}
+
+// {mu, gm's initial value} of every (column, group) up, the sums, {gm, m} down (not waited for)
+void FMChain::launch_hsums() {
+    const double beta_0 = 1.0, gamma_0 = 1.0, mu_0 = 0.0;
+    for (uint32_t c = 0; c <= K; ++c)
+        for (uint32_t q = 0; q < G; ++q) {
+            const double mu = c < K ? v_mu[(size_t)q * K + c] : w_mu[q];
+            h_mg[2 * ((size_t)c * G + q)] = mu;
+            h_mg[2 * ((size_t)c * G + q) + 1] = beta_0 * (mu - mu_0) * (mu - mu_0) + gamma_0;
         }
+    HIPCHK(hipMemcpyAsync(d_hmg.p, h_mg.data(), h_mg.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (d_gptr.p)
+        HIPCHK(fmg_group_sums(d_v.as<double>(), d_w.as<double>(), p, K, G, d_gptr.as<uint32_t>(), d_gidx.as<uint32_t>(),
+                              d_gfirst.as<uint32_t>(), d_hmg.as<double2>(), d_hsum.as<double2>(), st));
+    else
+        HIPCHK(fmm_hsums(d_v.as<double>(), d_w.as<double>(), p, K, d_hmg.as<double2>(), d_hsum.as<double2>(), st));
+    HIPCHK(hipMemcpyAsync(h_hs.data(), d_hsum.p, h_hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+void FMChain::group_sums(double* out) {
+    HIPCHK(hipStreamSynchronize(st));
+    ensure_group_lists();
+    const std::vector<double> keep = h_hs;  // a sweep's sums are read before the next launch: restored anyway
+    launch_hsums();
+    HIPCHK(hipStreamSynchronize(st));
+    std::copy(h_hs.begin(), h_hs.end(), out);
+    h_hs = keep;
+    if (G == 1 && grp.empty()) {  // an ungrouped chain keeps calling k_fmm_hsums
+        d_gptr.release();
+        d_gidx.release();
+        d_gfirst.release();
     }
 }
 
+void FMChain::upload_priors(bool vcols) {
+    if (!d_lm.p) return;
+    const uint32_t c0 = vcols ? 0 : K, c1 = vcols ? K : K + 1;
+    if (c0 == c1) return;
+    for (uint32_t c = c0; c < c1; ++c)
+        for (uint32_t q = 0; q < G; ++q) {
+            h_lm[2 * ((size_t)c * G + q)] = c < K ? v_lambda[(size_t)q * K + c] : w_lambda[q];
+            h_lm[2 * ((size_t)c * G + q) + 1] = c < K ? v_mu[(size_t)q * K + c] : w_mu[q];
+        }
+    HIPCHK(hipMemcpyAsync(d_lm.as<double>() + 2 * (size_t)c0 * G, h_lm.data() + 2 * (size_t)c0 * G,
+                          2 * (size_t)(c1 - c0) * G * sizeof(double), hipMemcpyHostToDevice, st));
+}
+
 // the normals of a pass, d[a * cols + f]: libFM consumes one per drawn attribute, f-major
-template <class G>
-void FMChain::fill_normals(G& g, DBuf& d, uint32_t cols, uint32_t tag) {
+template <class R>
+void FMChain::fill_normals(R& g, DBuf& d, uint32_t cols, uint32_t tag) {
     if (cfg.rng_mode != SBMF_RNG_REFERENCE) {
         HIPCHK(launch_philox_fill<double>(d.as<double>(), cols, 0, p, cfg.seed, it, tag, st));
         return;
@@ -102,23 +192,15 @@ void FMChain::fill_normals(G& g, DBuf& d, uint32_t cols, uint32_t tag) {
     HIPCHK(hipStreamSynchronize(st));  // z is a local
 }
 
-template <class G>
-void FMChain::sweep_draws(G& g) {
+template <class R>
+void FMChain::sweep_draws(R& g) {
     // ---- alpha and w0 (fm_learn_mcmc.h:901-929, :627-668)
     double s[2];
     residual_sums(s);
     if (do_multilevel) {
-        // the hyperparameter draws' column sums (fm_learn_mcmc.h:951-1089) on the device, in
+        // the hyperparameter draws' column sums (fm_learn_mcmc.h:931-1089) on the device, in
         // the host loops' order: w and v do not change before the draws that read them
-        const double beta_0 = 1.0, gamma_0 = 1.0, mu_0 = 0.0;
-        for (uint32_t c = 0; c <= K; ++c) {
-            const double mu = c < K ? v_mu[c] : w_mu;
-            h_mg[2 * c] = mu;
-            h_mg[2 * c + 1] = beta_0 * (mu - mu_0) * (mu - mu_0) + gamma_0;
-        }
-        HIPCHK(hipMemcpyAsync(d_hmg.p, h_mg.data(), h_mg.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(fmm_hsums(d_v.as<double>(), d_w.as<double>(), p, K, d_hmg.as<double2>(), d_hsum.as<double2>(), st));
-        HIPCHK(hipMemcpyAsync(h_hs.data(), d_hsum.p, h_hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        launch_hsums();
         ++n_launch;
     }
     HIPCHK(hipStreamSynchronize(st));
@@ -148,12 +230,14 @@ void FMChain::sweep_draws(G& g) {
     // ---- w (:422-457): group hyperparameters, then every attribute
     if (k1) {
         draw_hyper_w(g);
+        upload_priors(false);
         if (do_sample) fill_normals(g, d_zw, 1, TAG_FMC_W);
         w_pass();
     }
     // ---- v (:497-621): group hyperparameters of every factor, then factor by factor
     if (K) {
         draw_hyper_v(g);
+        upload_priors(true);
         if (do_sample) fill_normals(g, d_zv, K, TAG_FMC_V);
         for (uint32_t f = 0; f < K; ++f) v_pass(f);
     }
@@ -242,15 +326,39 @@ void FMChain::setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr,
     d_part.alloc((std::max<uint64_t>((nl + 255) / 256, 2 * ((nl + 1023) / 1024)) + 2) * sizeof(double));
     d_tpart.alloc((2 * ((nt + 255) / 256) + 2) * sizeof(double));
     d_res.alloc(8 * sizeof(double));
-    d_hmg.alloc(2 * ((size_t)K + 1) * sizeof(double));
-    d_hsum.alloc(2 * ((size_t)K + 1) * sizeof(double));
-    h_mg.assign(2 * ((size_t)K + 1), 0.0);
-    h_hs.assign(2 * ((size_t)K + 1), 0.0);
+    // the groups a learner set before this call (grp: [p], G = max + 1; empty: one group)
+    if (grp.empty()) G = 1;
+    cnt.assign(G, 0);
+    for (uint32_t a = 0; a < p; ++a) cnt[grp.empty() ? 0 : grp[a]]++;
+    d_hmg.alloc(2 * ((size_t)K + 1) * G * sizeof(double));
+    d_hsum.alloc(2 * ((size_t)K + 1) * G * sizeof(double));
+    h_mg.assign(2 * ((size_t)K + 1) * G, 0.0);
+    h_hs.assign(2 * ((size_t)K + 1) * G, 0.0);
+    if (!grp.empty()) {
+        ensure_group_lists();
+        grp_bytes = G <= 0x100u ? 1 : G <= 0x10000u ? 2 : 4;
+        const std::vector<uint8_t> g8(grp_bytes == 1 ? grp.begin() : grp.end(), grp.end());
+        const std::vector<uint16_t> g16(grp_bytes == 2 ? grp.begin() : grp.end(), grp.end());
+        if (grp_bytes == 1)
+            upload(d_grp, g8, st);
+        else if (grp_bytes == 2)
+            upload(d_grp, g16, st);
+        else
+            upload(d_grp, grp, st);
+        HIPCHK(hipStreamSynchronize(st));  // the narrowed copies are locals
+        d_lm.alloc(2 * ((size_t)K + 1) * G * sizeof(double));
+        h_lm.assign(2 * ((size_t)K + 1) * G, 0.0);
+    }
     d_scratch.alloc(((nl + 255) / 256 / 1024 + 16) * 2 * sizeof(double));
-    v_mu.assign(K, 0.0);
-    // fm_learn_mcmc::init (:1099-1116) and the -regular values (libfm.cpp:484-513)
-    w_lambda = c.regw;
-    v_lambda.assign(K, c.regv);
+    w_mu.assign(G, 0.0);
+    v_mu.assign((size_t)G * K, 0.0);
+    // fm_learn_mcmc::init (:1099-1116) and the -regular values (libfm.cpp:484-521): per group
+    w_lambda.assign(G, c.regw);
+    v_lambda.assign((size_t)G * K, c.regv);
+    for (uint32_t q = 0; q < G && !greg_w.empty(); ++q) {
+        w_lambda[q] = greg_w[q];
+        std::fill(v_lambda.begin() + (size_t)q * K, v_lambda.begin() + (size_t)(q + 1) * K, greg_v[q]);
+    }
     // model init and the starting predictions (fm_learn_mcmc_simultaneous.h:75-93)
     std::vector<double> h_w, h_v;  // host copies for the upload only
     if (c.rng_mode == SBMF_RNG_REFERENCE) {
@@ -283,11 +391,12 @@ void FMChain::predict_out(double* out) {
 
 void FMChain::hyper_out(double* h4k, double* alpha_out) {
     if (h4k) {
+        if (G > 1) fail(SBMF_E_STATE, "sbmf_get_hyper: this context has %u attribute groups; read them with sbmf_get_fm_groups", G);
         std::fill(h4k, h4k + 4 * (size_t)K, 0.0);
         std::copy(v_lambda.begin(), v_lambda.end(), h4k);
         std::copy(v_mu.begin(), v_mu.end(), h4k + K);
-        h4k[2 * K] = w_lambda;
-        if (K > 1) h4k[2 * K + 1] = w_mu;
+        h4k[2 * K] = w_lambda[0];
+        if (K > 1) h4k[2 * K + 1] = w_mu[0];
     }
     if (alpha_out) *alpha_out = alpha;
 }

@@ -9,6 +9,9 @@
 //   3. w group hyperparameters (host, sums on the device), then every w (the layout's pass)
 //   4. v group hyperparameters of every factor (host), then per factor f every v[f][.]
 //   5. re-predict train and test, running-mean test RMSE
+// With attribute groups (libFM's -meta; the general learner only) steps 3 and 4 draw one set of
+// hyperparameters per group, group by group in libFM's order, and every attribute is drawn
+// from its own group's prior.
 // Reference RNG mode replays the reference's glibc rand() stream draw for draw (rng.h): the
 // host draws the scalars in consumption order and fills the one normal per attribute of the w
 // and v passes ahead of the launches.  Philox mode fills those normals on the device.  ALS
@@ -35,8 +38,14 @@ struct FMChain {
     uint64_t N = 0, T = 0;          // train cases (all ranks), test cases
     int k0 = 1, k1 = 1, do_sample = 1, do_multilevel = 1;
     double lo = 1.0, hi = 5.0;  // the train target range (min/max_target)
-    double alpha = 1.0, w0 = 0.0, w_mu = 0.0, w_lambda = 0.0;
-    std::vector<double> v_mu, v_lambda;
+    double alpha = 1.0, w0 = 0.0;
+    // libFM's attribute groups (-meta, fm_learn_mcmc.h:931-1089): G groups, grp[a] the group of
+    // attribute a (empty: one group, every attribute), cnt[g] its attributes over all p ids.
+    // Hyperparameters per group: w_mu[g], w_lambda[g], v_mu[g * K + f], v_lambda[g * K + f].
+    // greg_w / greg_v: the groups' -regular precisions ([G] each; empty: cfg.regw / cfg.regv).
+    uint32_t G = 1;
+    std::vector<uint32_t> grp, cnt;
+    std::vector<double> w_mu, w_lambda, v_mu, v_lambda, greg_w, greg_v;
     uint32_t it = 0, n_launch = 0;
     uint32_t nranges = 0;   // the general learner's ranges (the two-attribute learner has none: 0)
     uint32_t I = 0, J = 0;  // users-first layout (user u -> attribute u, item i -> I + i); I = 0: cases, no such view
@@ -44,10 +53,19 @@ struct FMChain {
     hipStream_t st = nullptr;
     hipEvent_t ev[3] = {};
     DBuf d_w, d_v, d_vT, d_zw, d_zv, d_pthis, d_sum, d_part, d_tpart, d_res, d_scratch;
-    // the hyperparameter draws' sums (k_fmm_hsums): per v column f and for w (index K),
-    // {mu, gm's initial value} in, {gm, m} out
+    // the hyperparameter draws' sums (k_fmm_hsums; with groups k_fmg_gsums): per v column f and
+    // for w (index K), and within a column per group -- index c * G + g --, {mu, gm's initial
+    // value} in, {gm, m} out
     DBuf d_hmg, d_hsum;
     std::vector<double> h_mg, h_hs;
+    // with groups (G > 1): the members of every group ascending (d_gidx, group g's at
+    // [gptr[g], gptr[g+1])), d_gfirst[g] the first member of a contiguous group (its members
+    // are a plain range) or 0xffffffff, the attributes' groups in the narrowest integer that
+    // holds G (d_grp, grp_bytes wide), and the passes' priors {lambda, mu} of (column c, group
+    // g) at d_lm[c * G + g], uploaded after the hyperparameter draws
+    DBuf d_gptr, d_gidx, d_gfirst, d_grp, d_lm;
+    int grp_bytes = 0;
+    std::vector<double> h_lm;
 
     virtual ~FMChain();
 
@@ -79,24 +97,33 @@ struct FMChain {
     void predict_train();
     void run(uint32_t iters, sbmf_sweep_cb cb, void* user);
     void predict_out(double* out);                 // the -out predictions
-    void hyper_out(double* h4k, double* alpha_out);  // [v_lambda | v_mu | w_lambda,w_mu,0.. | 0]
+    void hyper_out(double* h4k, double* alpha_out);  // [v_lambda | v_mu | w_lambda,w_mu,0.. | 0]; one group only
+    // the column sums of the hyperparameter draws on the current model and mu through the grouped
+    // kernel (any G): out[(c * G + g) * 2 + {0: gm, 1: m}]
+    void group_sums(double* out);
     void model(double* w0_out, double* w, double* v);  // w[p], v[K][p]
     // the users-first layout read by user and item: v as [I][K] and [J][K], w as [I] and [J]
     // (rows at or past p read 0), w0; refused when the learner was given cases (I = 0)
     void factors(double* U, double* V);
     void biases(double* bu, double* bv, double* b0);
 
+protected:
+    // the priors of the w pass (c = K) or of every v pass (c = 0..K-1) to d_lm; a no-op without groups
+    void upload_priors(bool vcols);
+
 private:
-    template <class G>
-    void init_model(G& g, std::vector<double>& h_w, std::vector<double>& h_v);
-    template <class G>
-    void draw_hyper_w(G& g);
-    template <class G>
-    void draw_hyper_v(G& g);
-    template <class G>
-    void fill_normals(G& g, DBuf& d, uint32_t cols, uint32_t tag);
-    template <class G>
-    void sweep_draws(G& g);
+    void ensure_group_lists();
+    void launch_hsums();
+    template <class R>
+    void init_model(R& g, std::vector<double>& h_w, std::vector<double>& h_v);
+    template <class R>
+    void draw_hyper_w(R& g);
+    template <class R>
+    void draw_hyper_v(R& g);
+    template <class R>
+    void fill_normals(R& g, DBuf& d, uint32_t cols, uint32_t tag);
+    template <class R>
+    void sweep_draws(R& g);
 };
 
 // ---- rows by length, for both learners' pass launches

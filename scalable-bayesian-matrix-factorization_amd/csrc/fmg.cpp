@@ -71,6 +71,11 @@ struct FGLearner : FMChain {
         a.eq = d_eq.as<double2>();
         a.alpha = alpha;
         a.do_sample = do_sample;
+        if (d_lm.p) {  // attribute groups: the row's own prior, column c's at d_lm[c * G ..]
+            a.grp = d_grp.p;
+            a.grp_bytes = grp_bytes;
+            a.lm = d_lm.as<double2>() + (size_t)(vpass ? a.zoff : K) * G;
+        }
         for (const FGLaunch& l : launches) {
             a.rows = d_rows.as<uint32_t>() + l.r0;
             a.nrows = l.nrows;
@@ -138,8 +143,8 @@ struct FGLearner : FMChain {
         a.z = d_zw.as<double>();
         a.zs = 1;
         a.zoff = 0;
-        a.mu = w_mu;
-        a.lambda = w_lambda;
+        a.mu = w_mu[0];
+        a.lambda = w_lambda[0];
         run_pass(a, false);
     }
     void v_pass(uint32_t f) override {
@@ -198,7 +203,8 @@ struct OrderedCases {
     }
 };
 
-FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& tr_file, const sbmf_cases& te, hipStream_t st) {
+FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& tr_file, const sbmf_cases& te, hipStream_t st,
+                    const FMGroups* groups) {
     if (tr_file.n == 0) fail(SBMF_E_STATE, "no training cases");
     if (tr_file.n >= 0xffffffffull || te.n >= 0xffffffffull || tr_file.nnz >= 0xffffffffull || te.nnz >= 0xffffffffull)
         fail(SBMF_E_ARG, "more than 2^32-1 cases or features are not supported");
@@ -289,6 +295,21 @@ FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& tr_file, const sbmf_
     upload(L->d_aptr, aptr, st);
     upload(L->d_ent, ent, st);
     L->d_eq.alloc(tr.n * sizeof(double2));
+    if (groups && !groups->group.empty()) {
+        // group[a] for every attribute of num_attribute; one group is the ungrouped chain
+        if (groups->group.size() != p)
+            fail(SBMF_E_ARG, "sbmf_set_attr_groups gave %zu group ids; this context has num_attribute = %u "
+                             "(max(train, test num_attr) + 1)", groups->group.size(), p);
+        L->G = *std::max_element(groups->group.begin(), groups->group.end()) + 1;
+        if (L->G > 65535u) fail(SBMF_E_ARG, "%u attribute groups: at most 65535 are supported", L->G);
+        if (L->G > 1) L->grp = groups->group;
+    }
+    if (groups && !groups->regw.empty()) {
+        if (groups->regw.size() != L->G)
+            fail(SBMF_E_ARG, "sbmf_set_group_regular gave %zu groups; the context has %u", groups->regw.size(), L->G);
+        L->greg_w = groups->regw;
+        L->greg_v = groups->regv;
+    }
     L->setup(c, st, p, tr.n, tr.n, te.n, tr.target);
     L->n_launch = 0;
     return L.release();

@@ -43,6 +43,13 @@ struct FGPassArgs {
     const uint4* chunks;
     double2* sums;
     const double4* delta;
+    // attribute groups (-meta), last so that the fields above keep their places: grp[a] the
+    // group of attribute a, grp_bytes (1, 2 or 4) wide, and this pass's priors lm[g] = {lambda,
+    // mu}; a row then takes lm[grp[row]] in place of the scalars mu / lambda.  grp null: one
+    // group, the scalars.
+    const void* grp;
+    const double2* lm;
+    int grp_bytes;
 };
 // draw_w (:670-719) / draw_v (:780-835) over the rows of a launch, 64 / 256 / 1024 threads per row
 hipError_t fmg_wpass(const FGPassArgs& a, int threads_per_row, hipStream_t st);
@@ -51,6 +58,14 @@ hipError_t fmg_vpass(const FGPassArgs& a, int threads_per_row, hipStream_t st);
 // order, the draw, own written, delta[i] = {old, new, keep}
 hipError_t fmg_chunk_draw(const FGPassArgs& a, const uint32_t* rows, const uint32_t* cfirst, uint32_t nlong,
                           const double2* csums, int vpass, double4* delta, hipStream_t st);
+// The sums the hyperparameter draws (fm_learn_mcmc.h:931-1089) take over the attributes of one
+// group of one model column (v column c < K, w for c = K): out[c * G + g] = {gm, m}, gm from
+// mg[c * G + g].y adding (x_a - mg[c * G + g].x)^2, m from 0 adding x_a, over the group's
+// attributes in ascending id -- each one sequential chain without contraction, so the host loop's
+// bits.  Group g's members: gidx[gptr[g] .. gptr[g+1]) ascending, or the range from gfirst[g]
+// when gfirst[g] != 0xffffffff (a contiguous group).  One workgroup per (column, group).
+hipError_t fmg_group_sums(const double* v, const double* w, uint32_t p, uint32_t K, uint32_t G, const uint32_t* gptr,
+                          const uint32_t* gidx, const uint32_t* gfirst, const double2* mg, double2* out, hipStream_t st);
 // eq[c].q = sum over the case's entries (ascending attribute) of v_f[attr] * x  (add_main_q, :513-517)
 hipError_t fmg_q(const uint32_t* cptr, const uint32_t* cattr, const float* cx, uint64_t n, const double* vf,
                  double2* eq, hipStream_t st);
@@ -80,7 +95,14 @@ hipError_t fmg_predict_test(const FGPredictArgs& a, double it1, double* pthis, d
 
 // ---- host learner (fmg.cpp): libFM's chain (FMChain, fmc.h) on this layout, driven by the C ABI in sbmf.cpp
 struct FMChain;
-FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& train, const sbmf_cases& test, hipStream_t st);
+// libFM's attribute groups as the C ABI collects them: group[a] for every attribute (empty: one
+// group), the groups' -regular precisions (empty: cfg.regw / cfg.regv for every group)
+struct FMGroups {
+    std::vector<uint32_t> group;
+    std::vector<double> regw, regv;
+};
+FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& train, const sbmf_cases& test, hipStream_t st,
+                    const FMGroups* groups = nullptr);
 // the ranges of sbmf_fm_ranges over [0, p) (train cases; ids >= train.num_attr have no case)
 void fm_ranges(const sbmf_cases& train, uint32_t p, std::vector<uint32_t>& bounds);
 

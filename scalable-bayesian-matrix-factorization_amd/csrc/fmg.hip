@@ -23,13 +23,23 @@ __device__ __forceinline__ double wsum(double x) {  // xor butterfly: bit-identi
 
 // The row's draw from its sums m = sum h e, s2 = sum h^2 (fm_learn_mcmc.h:680-710, :793-824);
 // keep: a non-finite draw restores the old value (the reference returns before the update).
-template <int MODE>
+// GR: the prior is the row's group's (lm[grp[at]], one small load per row); else the launch's scalars.
+template <int MODE, bool GR>
 __device__ __forceinline__ double fmg_draw(const FGPassArgs& a, uint32_t at, double old, double m, double s2,
                                            bool& keep) {
 #pragma clang fp contract(off)
+    double lambda = a.lambda, mu = a.mu;
+    if constexpr (GR) {
+        const uint32_t g = a.grp_bytes == 1   ? static_cast<const uint8_t*>(a.grp)[at]
+                           : a.grp_bytes == 2 ? static_cast<const uint16_t*>(a.grp)[at]
+                                              : static_cast<const uint32_t*>(a.grp)[at];
+        const double2 t = a.lm[g];
+        lambda = t.x;
+        mu = t.y;
+    }
     if constexpr (MODE == 1) m -= old * s2;
-    s2 = 1.0 / (a.lambda + a.alpha * s2);
-    m = -s2 * (a.alpha * m - a.mu * a.lambda);
+    s2 = 1.0 / (lambda + a.alpha * s2);
+    m = -s2 * (a.alpha * m - mu * lambda);
     double nv;
     if (isnan(s2) || isinf(s2)) {
         nv = 0.0;
@@ -45,8 +55,8 @@ __device__ __forceinline__ double fmg_draw(const FGPassArgs& a, uint32_t at, dou
 
 // MODE 0: draw_w (fm_learn_mcmc.h:670-719); MODE 1: draw_v (:780-835).  NT threads per row; a
 // 256-thread block holds 256 / NT rows (NT <= 256) or one row (NT = 1024).
-template <int MODE, int NT>
-__global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_pass(FGPassArgs a) {
+template <int MODE, int NT, bool GR>
+__device__ __forceinline__ void fmg_pass_body(const FGPassArgs& a) {
 #pragma clang fp contract(off)
     constexpr int RPB = NT >= 256 ? 1 : 256 / NT;
     constexpr int NWR = NT >= 64 ? NT / 64 : 1;  // waves per row
@@ -142,7 +152,7 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_pass(FGPassArgs a) 
         nv = dl.y;
         keep = dl.z != 0.0;
     } else {
-        nv = fmg_draw<MODE>(a, row, old, m, s2, keep);
+        nv = fmg_draw<MODE, GR>(a, row, old, m, s2, keep);
         if (lt == 0) a.own[row] = nv;
     }
     if (keep) return;  // the reference returns before the update (:697-710, :811-824)
@@ -174,11 +184,21 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_pass(FGPassArgs a) 
     }
 }
 
+// k_fmg_pass: the launch's one prior; k_fmg_gpass: every row its group's (attribute groups)
+template <int MODE, int NT>
+__global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_pass(FGPassArgs a) {
+    fmg_pass_body<MODE, NT, false>(a);
+}
+template <int MODE, int NT>
+__global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_gpass(FGPassArgs a) {
+    fmg_pass_body<MODE, NT, true>(a);
+}
+
 // long rows in chunks: one thread per long row, chunk sums in chunk order, then the draw
-template <int MODE>
-__global__ __launch_bounds__(256) void k_fmg_chunk_draw(FGPassArgs a, const uint32_t* __restrict__ rows,
-                                                        const uint32_t* __restrict__ cfirst, uint32_t nlong,
-                                                        const double2* __restrict__ csums, double4* __restrict__ delta) {
+template <int MODE, bool GR>
+__device__ __forceinline__ void fmg_chunk_draw_body(const FGPassArgs& a, const uint32_t* __restrict__ rows,
+                                                    const uint32_t* __restrict__ cfirst, uint32_t nlong,
+                                                    const double2* __restrict__ csums, double4* __restrict__ delta) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nlong) return;
     double m = 0.0, s2 = 0.0;
@@ -189,9 +209,21 @@ __global__ __launch_bounds__(256) void k_fmg_chunk_draw(FGPassArgs a, const uint
     const uint32_t at = rows[i];
     const double old = a.own[at];
     bool keep;
-    const double nv = fmg_draw<MODE>(a, at, old, m, s2, keep);
+    const double nv = fmg_draw<MODE, GR>(a, at, old, m, s2, keep);
     a.own[at] = nv;
     delta[i] = make_double4(old, nv, keep ? 1.0 : 0.0, 0.0);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_fmg_chunk_draw(FGPassArgs a, const uint32_t* __restrict__ rows,
+                                                        const uint32_t* __restrict__ cfirst, uint32_t nlong,
+                                                        const double2* __restrict__ csums, double4* __restrict__ delta) {
+    fmg_chunk_draw_body<MODE, false>(a, rows, cfirst, nlong, csums, delta);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_fmg_gchunk_draw(FGPassArgs a, const uint32_t* __restrict__ rows,
+                                                         const uint32_t* __restrict__ cfirst, uint32_t nlong,
+                                                         const double2* __restrict__ csums, double4* __restrict__ delta) {
+    fmg_chunk_draw_body<MODE, true>(a, rows, cfirst, nlong, csums, delta);
 }
 
 __global__ __launch_bounds__(256) void k_fmg_q(const uint32_t* __restrict__ cptr, const uint32_t* __restrict__ cattr,
@@ -311,19 +343,29 @@ __global__ __launch_bounds__(256) void k_fmg_predict_test(FGPredictArgs a, doubl
     }
 }
 
-template <int MODE>
+template <int MODE, bool GR>
 hipError_t launch_pass(const FGPassArgs& a, int tpr, hipStream_t st) {
     if (a.nrows == 0) return hipSuccess;
     if (a.xmode != 0 && !a.chunks) return hipErrorInvalidValue;
+    if (GR && (!a.lm || (a.grp_bytes != 1 && a.grp_bytes != 2 && a.grp_bytes != 4))) return hipErrorInvalidValue;
     switch (tpr) {
         case 64:
-            k_fmg_pass<MODE, 64><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
+            if (GR)
+                k_fmg_gpass<MODE, 64><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
+            else
+                k_fmg_pass<MODE, 64><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
             break;
         case 256:
-            k_fmg_pass<MODE, 256><<<a.nrows, 256, 0, st>>>(a);
+            if (GR)
+                k_fmg_gpass<MODE, 256><<<a.nrows, 256, 0, st>>>(a);
+            else
+                k_fmg_pass<MODE, 256><<<a.nrows, 256, 0, st>>>(a);
             break;
         case 1024:
-            k_fmg_pass<MODE, 1024><<<a.nrows, 1024, 0, st>>>(a);
+            if (GR)
+                k_fmg_gpass<MODE, 1024><<<a.nrows, 1024, 0, st>>>(a);
+            else
+                k_fmg_pass<MODE, 1024><<<a.nrows, 1024, 0, st>>>(a);
             break;
         default:
             return hipErrorInvalidValue;
@@ -331,18 +373,98 @@ hipError_t launch_pass(const FGPassArgs& a, int tpr, hipStream_t st) {
     return hipGetLastError();
 }
 
+// The grouped form of k_fmm_hsums (fmm.hip): block (c, g) runs the two chains of group g of
+// column c.  The workgroup stages 1024-value chunks of the group's values and their squared
+// deviations in LDS (double-buffered, 32 KiB: four groups' workgroups share a CU's 160 KiB where
+// k_fmm_hsums' 64 KiB admit two); lane 0 runs the gm chain and lane 1 the m chain.  A contiguous
+// group reads its range, any other gathers through its ascending member list.
+__global__ __launch_bounds__(256) void k_fmg_gsums(const double* __restrict__ v, const double* __restrict__ w,
+                                                   uint32_t p, uint32_t K, uint32_t G,
+                                                   const uint32_t* __restrict__ gptr, const uint32_t* __restrict__ gidx,
+                                                   const uint32_t* __restrict__ gfirst, const double2* __restrict__ mg,
+                                                   double2* __restrict__ out) {
+#pragma clang fp contract(off)
+    constexpr uint32_t CH = 1024;
+    __shared__ __align__(16) double xs[2][CH];
+    __shared__ __align__(16) double ds[2][CH];
+    const uint32_t c = blockIdx.x, g = blockIdx.y;
+    const double* __restrict__ x = c < K ? v + (size_t)c * p : w;
+    const uint32_t b0 = gptr[g], cnt = gptr[g + 1] - b0, first = gfirst[g];
+    const double2 in = mg[(size_t)c * G + g];
+    const double mu = in.x;
+    double acc = threadIdx.x == 0 ? in.y : 0.0;  // lane 0: gm, lane 1: m
+    const uint32_t nch = (cnt + CH - 1) / CH;
+    auto stage = [&](uint32_t ch, int b) {
+        for (uint32_t i = threadIdx.x; i < CH; i += 256) {
+            const uint32_t q = ch * CH + i;
+            double t = 0.0;
+            if (q < cnt) {
+                const uint32_t at = first != 0xffffffffu ? first + q : gidx[b0 + q];
+                if (at < p) t = x[at];
+            }
+            const double d = t - mu;
+            xs[b][i] = t;
+            ds[b][i] = d * d;
+        }
+    };
+    stage(0, 0);
+    __syncthreads();
+    for (uint32_t ch = 0; ch < nch; ++ch) {
+        const int b = ch & 1;
+        if (ch + 1 < nch) stage(ch + 1, b ^ 1);
+        if (threadIdx.x < 2) {
+            const double* __restrict__ src = threadIdx.x == 0 ? ds[b] : xs[b];
+            const uint32_t n = min(CH, cnt - ch * CH);
+            uint32_t j = 0;
+            for (; j + 32 <= n; j += 32) {
+                double2 t[16];  // 16-byte LDS reads, all issued before the first add
+#pragma unroll
+                for (int u = 0; u < 16; ++u) t[u] = reinterpret_cast<const double2*>(src + j)[u];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    acc = acc + t[u].x;
+                    acc = acc + t[u].y;
+                }
+            }
+            for (; j < n; ++j) acc = acc + src[j];
+        }
+        __syncthreads();
+    }
+    __shared__ double res[2];
+    if (threadIdx.x < 2) res[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[(size_t)c * G + g] = make_double2(res[0], res[1]);
+}
+
 }  // namespace
 
-hipError_t fmg_wpass(const FGPassArgs& a, int tpr, hipStream_t st) { return launch_pass<0>(a, tpr, st); }
-hipError_t fmg_vpass(const FGPassArgs& a, int tpr, hipStream_t st) { return launch_pass<1>(a, tpr, st); }
+hipError_t fmg_wpass(const FGPassArgs& a, int tpr, hipStream_t st) {
+    return a.grp ? launch_pass<0, true>(a, tpr, st) : launch_pass<0, false>(a, tpr, st);
+}
+hipError_t fmg_vpass(const FGPassArgs& a, int tpr, hipStream_t st) {
+    return a.grp ? launch_pass<1, true>(a, tpr, st) : launch_pass<1, false>(a, tpr, st);
+}
+
+hipError_t fmg_group_sums(const double* v, const double* w, uint32_t p, uint32_t K, uint32_t G, const uint32_t* gptr,
+                          const uint32_t* gidx, const uint32_t* gfirst, const double2* mg, double2* out, hipStream_t st) {
+    if (G == 0 || G > 65535u) return hipErrorInvalidValue;  // the grid's y extent
+    k_fmg_gsums<<<dim3(K + 1, G), 256, 0, st>>>(v, w, p, K, G, gptr, gidx, gfirst, mg, out);
+    return hipGetLastError();
+}
 
 hipError_t fmg_chunk_draw(const FGPassArgs& a, const uint32_t* rows, const uint32_t* cfirst, uint32_t nlong,
                           const double2* csums, int vpass, double4* delta, hipStream_t st) {
     if (nlong == 0) return hipSuccess;
-    if (vpass)
-        k_fmg_chunk_draw<1><<<(nlong + 255) / 256, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
+    if (a.grp && (!a.lm || (a.grp_bytes != 1 && a.grp_bytes != 2 && a.grp_bytes != 4))) return hipErrorInvalidValue;
+    const dim3 grid((nlong + 255) / 256);
+    if (vpass && a.grp)
+        k_fmg_gchunk_draw<1><<<grid, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
+    else if (vpass)
+        k_fmg_chunk_draw<1><<<grid, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
+    else if (a.grp)
+        k_fmg_gchunk_draw<0><<<grid, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
     else
-        k_fmg_chunk_draw<0><<<(nlong + 255) / 256, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
+        k_fmg_chunk_draw<0><<<grid, 256, 0, st>>>(a, rows, cfirst, nlong, csums, delta);
     return hipGetLastError();
 }
 

@@ -208,8 +208,8 @@ struct FMLearner : FMChain {
             a.z = d_zw.as<double>();
             a.zs = 1;
             a.zoff = 0;
-            a.mu = w_mu;
-            a.lambda = w_lambda;
+            a.mu = w_mu[0];
+            a.lambda = w_lambda[0];
             run_bins(a, side == 1, false);
         }
     }

@@ -1143,6 +1143,40 @@ void sbmf_free_cases(sbmf_cases* c) {
     std::memset(c, 0, sizeof *c);
 }
 
+// DataMetaInfo::loadGroupsFromFile (Data.h:49-61): DVector<uint>::load reads num_attr values with
+// operator>>.  Where that reads past the end or meets something that is no number (and goes on
+// with what it has), this refuses, naming the entry.
+int sbmf_load_libfm_meta(const char* path, uint32_t num_attr, uint32_t* group, uint32_t* G) {
+    if (!path || (num_attr && !group)) return SBMF_E_ARG;
+    InFile f;
+    if (!open_in(path, f)) {
+        g_lerr = std::string("unable to open ") + path;
+        return SBMF_E_IO;
+    }
+    const char *q = f.p, *end = f.p + f.n;
+    uint32_t mx = 0;
+    for (uint32_t a = 0; a < num_attr; ++a) {
+        while (q < end && (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r' || *q == '\f' || *q == '\v')) ++q;
+        if (q == end) {
+            g_lerr = std::string(path) + " holds " + std::to_string(a) + " group ids; " + std::to_string(num_attr) +
+                     " attributes need one each (entry " + std::to_string(a + 1) + " is missing)";
+            return SBMF_E_IO;
+        }
+        uint64_t v = 0;
+        const char* b = q;
+        while (q < end && *q >= '0' && *q <= '9' && v <= 0xffffffffull) v = v * 10 + (uint64_t)(*q++ - '0');
+        const bool sep = q == end || *q == ' ' || *q == '\t' || *q == '\n' || *q == '\r' || *q == '\f' || *q == '\v';
+        if (q == b || !sep || v > 0xfffffffeull) {
+            g_lerr = std::string(path) + ": entry " + std::to_string(a + 1) + " is not a group id (an unsigned integer)";
+            return SBMF_E_IO;
+        }
+        group[a] = (uint32_t)v;
+        mx = std::max(mx, (uint32_t)v);
+    }
+    if (G) *G = num_attr ? mx + 1 : 0;
+    return SBMF_OK;
+}
+
 int sbmf_load_libfm_cases(const char* path, sbmf_cases* out) {
     if (!path || !out) return SBMF_E_ARG;
     std::memset(out, 0, sizeof *out);

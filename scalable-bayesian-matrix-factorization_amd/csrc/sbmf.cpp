@@ -318,7 +318,7 @@ static void prepare_cases(sbmf_ctx* c, bool triples) {
         sbmf::fail(SBMF_E_STATE, "the general libFM learner (cases with any number of features) runs on one rank: "
                                  "this context joined a communicator or is a virtual rank");
     c->K = c->cfg.num_factor;
-    c->fm = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st);
+    c->fm = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st, &c->fmgroups);
     if (triples) {  // the users-first layout: the model reads back by user / item
         c->fm->I = c->I;
         c->fm->J = c->J;
@@ -372,8 +372,11 @@ static void prepare_ctx(sbmf_ctx* c) {
         return;
     }
     sbmf::Comm* comm = c->nranks > 1 ? c->comm : nullptr;
+    // a triples context given attribute groups takes the general learner: the two-attribute
+    // kernels (fmm.hip) keep one group
     const char* gen = std::getenv("SBMF_FMM_GENERAL");
-    if (libfm_method(c) && gen && std::atoi(gen) != 0) {
+    const bool grouped = !c->fmgroups.group.empty() || !c->fmgroups.regw.empty();
+    if (libfm_method(c) && ((gen && std::atoi(gen) != 0) || grouped)) {
         triples_to_cases(c->tu, c->ti, c->tr, c->I, c->ctr);
         triples_to_cases(c->su, c->si, c->sr, c->I, c->cte);
         prepare_cases(c, true);
@@ -501,6 +504,81 @@ int sbmf_fm_info(sbmf_ctx* ctx, uint32_t* num_attr, uint32_t* nranges, uint32_t*
     if (num_attr) *num_attr = ctx->fm->p;
     if (nranges) *nranges = ctx->fm->nranges;
     if (launches_per_iter) *launches_per_iter = ctx->fm->n_launch;
+    API_END(ctx)
+}
+
+// ---- libFM's attribute groups (-meta)
+static void check_groups_ctx(sbmf_ctx* ctx, const char* fn) {
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (ctx->prepared) sbmf::fail(SBMF_E_STATE, "%s: data already prepared", fn);
+    static const char* const names[] = {"mcmc (the SBPMF sampler)", "vb (online VB)", "mcmc, libFM order", "als"};
+    if (ctx->virt) sbmf::fail(SBMF_E_STATE, "%s: this context is a virtual rank; attribute groups run on one rank", fn);
+    if (ctx->nranks > 1 || ctx->comm != &ctx->own_comm || ctx->own_comm.active())
+        sbmf::fail(SBMF_E_STATE, "%s: this context joined a communicator; attribute groups run on one rank", fn);
+    if (!libfm_method(ctx))
+        sbmf::fail(SBMF_E_STATE, "%s: attribute groups belong to libFM's MCMC / ALS learner (SBMF_METHOD_LIBFM_MCMC, "
+                                 "SBMF_METHOD_ALS); this context runs method %s", fn, names[ctx->cfg.method]);
+}
+
+int sbmf_set_attr_groups(sbmf_ctx* ctx, uint32_t n, const uint32_t* group) {
+    API_BEGIN
+    check_groups_ctx(ctx, "sbmf_set_attr_groups");
+    if (n && !group) sbmf::fail(SBMF_E_ARG, "sbmf_set_attr_groups: null array with n > 0");
+    // with the data already given the count is checked here, else at sbmf_prepare
+    uint64_t p = 0;
+    if (ctx->ctr.set) {
+        p = (uint64_t)std::max(ctx->ctr.num_attr, ctx->cte.set ? ctx->cte.num_attr : 0u) + 1;
+    } else if (!ctx->tu.empty()) {
+        uint32_t umax = 0, imax = 0;
+        for (size_t x = 0; x < ctx->tu.size(); ++x) umax = std::max(umax, ctx->tu[x]), imax = std::max(imax, ctx->ti[x]);
+        for (size_t x = 0; x < ctx->su.size(); ++x) umax = std::max(umax, ctx->su[x]), imax = std::max(imax, ctx->si[x]);
+        p = (uint64_t)std::max(ctx->I_req, umax + 1) + imax + 2;
+    }
+    if (n && p && n != p)
+        sbmf::fail(SBMF_E_ARG, "sbmf_set_attr_groups: %u group ids given, the context's num_attribute is %llu (largest "
+                               "attribute id over train and test + 2)", n, (unsigned long long)p);
+    ctx->fmgroups.group.assign(group, group + n);
+    API_END(ctx)
+}
+
+int sbmf_set_group_regular(sbmf_ctx* ctx, uint32_t G, const double* regw, const double* regv) {
+    API_BEGIN
+    check_groups_ctx(ctx, "sbmf_set_group_regular");
+    if (G && (!regw || !regv)) sbmf::fail(SBMF_E_ARG, "sbmf_set_group_regular: null array with G > 0");
+    if (!ctx->fmgroups.group.empty()) {
+        const uint32_t have = *std::max_element(ctx->fmgroups.group.begin(), ctx->fmgroups.group.end()) + 1;
+        if (G && G != have)
+            sbmf::fail(SBMF_E_ARG, "sbmf_set_group_regular: %u groups given, sbmf_set_attr_groups set %u", G, have);
+    }
+    ctx->fmgroups.regw.assign(regw, regw + G);
+    ctx->fmgroups.regv.assign(regv, regv + G);
+    API_END(ctx)
+}
+
+int sbmf_get_fm_groups(sbmf_ctx* ctx, uint32_t* G, uint32_t* cnt, double* w_lambda, double* w_mu, double* v_lambda,
+                       double* v_mu) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
+    if (!ctx->fm) sbmf::fail(SBMF_E_STATE, "sbmf_get_fm_groups: this context does not run libFM's MCMC / ALS learner");
+    const sbmf::FMChain& f = *ctx->fm;
+    if (G) *G = f.G;
+    if (cnt) std::copy(f.cnt.begin(), f.cnt.end(), cnt);
+    if (w_lambda) std::copy(f.w_lambda.begin(), f.w_lambda.end(), w_lambda);
+    if (w_mu) std::copy(f.w_mu.begin(), f.w_mu.end(), w_mu);
+    if (v_lambda) std::copy(f.v_lambda.begin(), f.v_lambda.end(), v_lambda);
+    if (v_mu) std::copy(f.v_mu.begin(), f.v_mu.end(), v_mu);
+    API_END(ctx)
+}
+
+int sbmf_test_fm_group_sums(sbmf_ctx* ctx, double* out) {
+    API_BEGIN
+    if (!ctx || !out) sbmf::fail(SBMF_E_ARG, "null argument");
+    if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
+    if (!ctx->fm || !ctx->fm->nranges)
+        sbmf::fail(SBMF_E_STATE, "sbmf_test_fm_group_sums: this context does not run the general libFM learner");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    ctx->fm->group_sums(out);
     API_END(ctx)
 }
 

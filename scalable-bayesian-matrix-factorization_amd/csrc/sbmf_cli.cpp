@@ -9,7 +9,9 @@
 //   "#Iter=%3d\tTrain=<rmse>\tTest=<rmse>"                      (:244)
 // -method mcmc (libFM order) and -method als read libFM text with any number of features per
 // case (sbmf_load_libfm_cases -> the general learner, fmg.cpp); a file of "user:1 item:1"
-// cases takes the two-attribute learner.
+// cases takes the two-attribute learner.  -meta FILE (one attribute group id per attribute)
+// gives those two methods libFM's per-group hyperparameters (sbmf_set_attr_groups; -regular then
+// also takes 1 + 2G values); a two-feature file with -meta takes the general learner.
 // and the file test_rmse_<k0><k1><K>_<method> (truncated at start, one
 // running-mean test RMSE per line, :57-62,146); -out writes one averaged
 // prediction per test line (libfm.cpp:629-634).
@@ -198,7 +200,8 @@ uint32_t users_first_offset(sbmf_ratings& tr, sbmf_ratings& te) {
 struct RunState {
     std::string rmse_file;
     bool vb = false;  // online VB prints "#Iter=..\tTest=.." (fm_learn_vb_online_simultaneous.h:447)
-    bool lfm = false;  // libFM's fm_learn_mcmc chain: one attribute group with w (fm_learn_mcmc.h:1140-1149)
+    bool lfm = false;  // libFM's fm_learn_mcmc chain: one attribute group with w (fm_learn_mcmc.h:1140-1149) ...
+    uint32_t G = 1;    // ... or the -meta file's
     bool k1 = false;   // -dim k1: libFM logs wmu / wlambda (fm_learn_mcmc.h:422-431)
     bool avg_collected = false;  // the running mean divides by the collected sweeps
     uint32_t K = 0, ncol = 0;
@@ -220,7 +223,7 @@ struct RunState {
 void rlog_header(std::ostream& o, const RunState& rs) {
     o << "rmse\tmae\ttime_pred\ttime_learn\ttime_learn2\ttime_learn4\talpha\trmse_mcmc_this\trmse_mcmc_all";
     if (!rs.vb) o << "\trmse_mcmc_all_but5";
-    const int ng = (rs.lfm || rs.vb) ? 1 : 2;
+    const int ng = rs.lfm ? (int)rs.G : rs.vb ? 1 : 2;
     for (int g = 0; g < ng; ++g) {
         o << "\twmu[" << g << "]\twlambda[" << g << "]";
         for (uint32_t f = 0; f < rs.K; ++f) o << "\tvmu[" << g << "," << f << "]\tvlambda[" << g << "," << f << "]";
@@ -278,13 +281,23 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
     o << (rs.vb ? nan : in->rmse_avg) << "\t" << mae << "\t" << nan << "\t" << tl << "\t" << tl << "\t" << tl << "\t";
     std::vector<double> h(4 * (size_t)rs.K, nan);
     double alpha = nan;
-    if (!rs.vb && sbmf_get_hyper(rs.ctx, h.data(), &alpha) != SBMF_OK) throw std::runtime_error(sbmf_last_error(rs.ctx));
+    if (!rs.vb && sbmf_get_hyper(rs.ctx, rs.lfm && rs.G > 1 ? nullptr : h.data(), &alpha) != SBMF_OK)
+        throw std::runtime_error(sbmf_last_error(rs.ctx));
     o << (rs.vb ? nan : alpha) << "\t" << in->rmse_this << "\t" << (rs.vb ? nan : in->rmse_avg);
     if (!rs.vb) o << "\t" << rmse_but5;
     const uint32_t K = rs.K;
     if (rs.vb) {
         o << "\t" << nan << "\t" << nan;
         for (uint32_t f = 0; f < K; ++f) o << "\t" << nan << "\t" << nan;
+    } else if (rs.lfm && rs.G > 1) {  // the -meta groups, group-major as libFM registers them (fm_learn_mcmc.h:1140-1149)
+        const uint32_t G = rs.G;
+        std::vector<double> wl(G), wm(G), vl((size_t)G * K), vm((size_t)G * K);
+        if (sbmf_get_fm_groups(rs.ctx, nullptr, nullptr, wl.data(), wm.data(), vl.data(), vm.data()) != SBMF_OK)
+            throw std::runtime_error(sbmf_last_error(rs.ctx));
+        for (uint32_t g = 0; g < G; ++g) {
+            o << "\t" << (rs.k1 ? wm[g] : nan) << "\t" << (rs.k1 ? wl[g] : nan);
+            for (uint32_t f = 0; f < K; ++f) o << "\t" << vm[(size_t)g * K + f] << "\t" << vl[(size_t)g * K + f];
+        }
     } else if (rs.lfm) {  // sbmf_get_hyper: [v_lambda | v_mu | w_lambda, w_mu | 0]
         o << "\t" << (rs.k1 ? h[2 * K + (K > 1 ? 1 : 0)] : nan) << "\t" << (rs.k1 ? h[2 * K] : nan);
         for (uint32_t f = 0; f < K; ++f) o << "\t" << h[K + f] << "\t" << h[f];
@@ -323,6 +336,37 @@ int on_sweep(const sbmf_sweep_info* in, void* user) {
 // fault it skipped under rocprofv3 came with RCCL linked at load time; libsbmf
 // dlopens RCCL only for a multi-GPU communicator now, and the CLI exits normally
 // under rocprofv3 (profiles/r04/r04s2_cli_rocprof_kernel_stats.csv).
+// -regular for libFM's learners (libfm.cpp:484-521): none, one value for all, 'r0,r1,r2', or with
+// G -meta groups 'r0, w_lambda[0..G-1], v_lambda[0..G-1]' (1 + 2G values; for G = 1 the two
+// readings of three values coincide).  gw / gv stay empty unless the per-group form was given.
+void parse_regular(const std::string& text, uint32_t G, double& r0, double& rw, double& rv, std::vector<double>& gw,
+                   std::vector<double>& gv) {
+    std::vector<double> reg;
+    for (const std::string& x : split_strs(text)) reg.push_back(std::stod(x));
+    r0 = rw = rv = 0.0;
+    gw.clear();
+    gv.clear();
+    if (reg.empty()) return;
+    if (reg.size() == 1) {
+        r0 = rw = rv = reg[0];
+    } else if (reg.size() == 3) {
+        r0 = reg[0];
+        rw = reg[1];
+        rv = reg[2];
+    } else if (G > 1 && reg.size() == 1 + 2 * (size_t)G) {
+        r0 = reg[0];
+        gw.assign(reg.begin() + 1, reg.begin() + 1 + G);
+        gv.assign(reg.begin() + 1 + G, reg.end());
+    } else {
+        std::ostringstream m;
+        m << "-regular takes 'r', 'r0,r1,r2'";
+        if (G > 1) m << " or, with the " << G << " groups of -meta, " << 1 + 2 * (size_t)G << " values 'r0,w_lambda[g]..,v_lambda[g]..'";
+        else m << " (1 + 2G values need the G groups of a -meta file)";
+        m << "; " << reg.size() << " given";
+        throw std::runtime_error(m.str());
+    }
+}
+
 bool g_guarded = false;
 int leave(int rc) {
     std::cout.flush();
@@ -343,14 +387,18 @@ int main(int argc, char** argv) {
                   << "----------------------------------------------------------------------------" << std::endl;
         // libFM's flags (libfm.cpp:86-111)
         cl.reg("task", "r=regression [MANDATORY]");
-        cl.reg("meta", "filename for meta information about data set (ignored: one user and one item group)");
+        cl.reg("meta", "filename with one attribute group id per attribute (libFM's -meta): -method mcmc (libFM order) "
+                       "and -method als draw their hyperparameters per group, and a two-feature input then takes the "
+                       "general learner; ignored by the SBPMF sampler (-order sbpmf: one user and one item group) and "
+                       "by -method vb");
         cl.reg("train", "filename for training data [MANDATORY] (SBPMF triples or libFM text)");
         cl.reg("test", "filename for test data [MANDATORY]");
         cl.reg("validation", "unused (SGDA only in libFM)");
         cl.reg("out", "filename for output: averaged test predictions");
         cl.reg("dim", "'k0,k1,k2': k0=use bias, k1=use 1-way interactions, k2=dim of 2-way interactions; default=1,1,8");
         cl.reg("regular", "'r0,r1,r2' (or one value for all) for -method als and -method mcmc -order libfm: "
-                          "fixed / starting precisions of w0, w, v (libfm.cpp:484-513); default=0");
+                          "fixed / starting precisions of w0, w, v (libfm.cpp:484-513); with the G groups of -meta also "
+                          "'r0,w[0],..,w[G-1],v[0],..,v[G-1]' (1 + 2G values, :514-521); default=0");
         cl.reg("init_stdev", "stdev for initialization of the factors; default: 1.0 (quirks final) / 0.1 (sbpmf2)");
         cl.reg("stdev", "unused");
         cl.reg("iter", "number of collection sweeps; default=100");
@@ -508,16 +556,6 @@ int main(int argc, char** argv) {
         if (lfm) {
             cfg.libfm_dim = (dim[0] ? 1u : 0u) | (dim[1] ? 2u : 0u);
             if (!cl.has("init_stdev")) cfg.init_stdev = 0.1;  // libfm.cpp:127
-            std::vector<double> reg;
-            for (const std::string& x : split_strs(cl.get("regular", ""))) reg.push_back(std::stod(x));
-            if (reg.size() == 1) reg = {reg[0], reg[0], reg[0]};
-            if (!reg.empty() && reg.size() != 3)
-                throw std::runtime_error("-regular takes 'r' or 'r0,r1,r2' (no -meta groups in this build)");
-            if (reg.size() == 3) {
-                cfg.reg0 = reg[0];
-                cfg.regw = reg[1];
-                cfg.regv = reg[2];
-            }
         }
         cfg.eval_test = 1;
 
@@ -566,6 +604,31 @@ int main(int argc, char** argv) {
         // item offset num_user, so no flag is needed (-item_offset overrides it).
         // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
         if ((lfm || vb || rec || recg) && libfm_input && !cl.has("item_offset") && !general) off = users_first_offset(tr, te);
+        // -meta and -regular (libFM's learners): one group id per attribute of num_attribute = the
+        // largest feature id over train and test + 2 (libfm.cpp:328-335)
+        std::vector<uint32_t> meta;
+        std::vector<double> greg_w, greg_v;
+        uint32_t nmeta_groups = 1;
+        const bool grouped = lfm && cl.has("meta") && !cl.get("meta", "").empty();
+        if (grouped) {
+            uint64_t na = 0;
+            if (general) {
+                na = (uint64_t)std::max(ctr.num_attr, cte.num_attr) + 1;
+            } else {
+                uint64_t umax = 0, imax = 0;
+                for (const sbmf_ratings* r : {&tr, &te})
+                    for (uint64_t x = 0; x < r->n; ++x) {
+                        umax = std::max<uint64_t>(umax, r->user[x]);
+                        imax = std::max<uint64_t>(imax, r->item[x]);
+                    }
+                na = std::max<uint64_t>(off, umax + 1) + imax + 2;
+            }
+            if (na > 0xfffffffeull) throw std::runtime_error("attribute id too large");
+            meta.resize(na);
+            if (sbmf_load_libfm_meta(cl.get("meta", "").c_str(), (uint32_t)na, meta.data(), &nmeta_groups) != SBMF_OK)
+                throw std::runtime_error(std::string("-meta: ") + sbmf_loader_error());
+        }
+        if (lfm) parse_regular(cl.get("regular", ""), nmeta_groups, cfg.reg0, cfg.regw, cfg.regv, greg_w, greg_v);
         std::vector<uint32_t> rec_ids;
         if (rec) {
             std::ifstream f(cl.get("rec_users", ""));
@@ -630,11 +693,27 @@ int main(int argc, char** argv) {
             // (inferred or given) item offset on
             if ((lfm || vb) && off) chk(sbmf_set_dims(ctx, off, 0));
         }
+        if (grouped) {
+            chk(sbmf_set_attr_groups(ctx, (uint32_t)meta.size(), meta.data()));
+            if (!greg_w.empty()) chk(sbmf_set_group_regular(ctx, nmeta_groups, greg_w.data(), greg_v.data()));
+        }
         chk(sbmf_prepare(ctx));
         uint32_t nu, ni;
         uint64_t ntr, nte;
         chk(sbmf_get_dims(ctx, &nu, &ni, &ntr, &nte));
-        if (general) {
+        if (grouped) {  // DataMetaInfo::debug (Data.h:63-68)
+            std::vector<uint32_t> cnt(nmeta_groups);
+            chk(sbmf_get_fm_groups(ctx, nullptr, cnt.data(), nullptr, nullptr, nullptr, nullptr));
+            std::cout << "#attr=" << meta.size() << "\t#groups=" << nmeta_groups << std::endl;
+            for (uint32_t g = 0; g < nmeta_groups && cl.getl("verbosity", 0) > 0; ++g)
+                std::cout << "#attr_in_group[" << g << "]=" << cnt[g] << std::endl;
+        }
+        if (!general && grouped) {  // the triples through the general learner
+            uint32_t na = 0, nr = 0;
+            chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
+            std::cout << "#users=" << nu << "\t#items=" << ni << "\t#attributes=" << na << "\t#ranges=" << nr
+                      << "\t#train=" << ntr << "\t#test=" << nte << "\tK=" << cfg.num_factor << std::endl;
+        } else if (general) {
             uint32_t na = 0, nr = 0;
             chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
             std::cout << "#attributes=" << na << "\t#ranges=" << nr << "\t#train=" << ntr << "\t#test=" << nte
@@ -651,6 +730,7 @@ int main(int argc, char** argv) {
         rs.rmse_file = "test_rmse_" + nm.str() + "_" + (vb ? std::string("vb_online") : std::string("mcmc"));
         rs.vb = vb;
         rs.lfm = lfm;
+        rs.G = grouped ? nmeta_groups : 1;
         rs.k1 = dim[1] != 0;
         rs.K = cfg.num_factor;
         rs.ctx = ctx;

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "load_libfm_cases", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -119,6 +119,35 @@ def load_libfm_cases(path):
                      arr(c.target, n, np.float32), num_attr=int(c.num_attr))
     finally:
         lib.sbmf_free_cases(C.byref(c))
+
+
+def load_libfm_meta(path, num_attr):
+    """A libFM -meta file (sbmf_load_libfm_meta): the group ids (uint32 [num_attr]) of the first
+    num_attr whitespace-separated entries; fewer entries or a non-number raise SBMFError (SBMF_E_IO)."""
+    out, G = np.zeros(int(num_attr), dtype=np.uint32), C.c_uint32()
+    rc = lib.sbmf_load_libfm_meta(str(path).encode(), int(num_attr), _ptr(out, C.c_uint32), C.byref(G))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_loader_error().decode())
+    return out
+
+
+def parse_regular(regular, num_groups=1):
+    """libFM's -regular (libfm.cpp:484-521) as (reg0, regw, regv, group_regw, group_regv): no value
+    (all 0), one value for all, (r0, r1, r2), or with G = num_groups > 1 groups the 1 + 2G values
+    (r0, w_lambda[0..G-1], v_lambda[0..G-1]); the group lists are None unless that form was given.
+    For one group the two readings of three values coincide.  Any other count: ValueError."""
+    r = [float(x) for x in (regular if np.ndim(regular) else [regular])]
+    G = int(num_groups)
+    if len(r) == 0:
+        return 0.0, 0.0, 0.0, None, None
+    if len(r) == 1:
+        return r[0], r[0], r[0], None, None
+    if len(r) == 3:
+        return r[0], r[1], r[2], None, None
+    if G > 1 and len(r) == 1 + 2 * G:
+        return r[0], 0.0, 0.0, r[1:1 + G], r[1 + G:]
+    raise ValueError("regular takes 0, 1 or 3 values, or 1 + 2G = %d with the %d attribute groups set; %d given"
+                     % (1 + 2 * G, G, len(r)))
 
 
 def fm_ranges(train, num_attr=None):
@@ -274,7 +303,9 @@ class FMLearnSBPMF:
         """method "mcmc" with order "sbpmf" (default): the SBPMF Gibbs sampler;
         method "mcmc" with order "libfm": libFM's own MCMC chain (f-outer, one
         hyperprior group, w0 / w with k0 / k1, -regular = ``regular``);
-        "als": libFM's ALS (the same learner without sampling); "vb": online VB."""
+        "als": libFM's ALS (the same learner without sampling); "vb": online VB.
+        With attribute groups (``set_groups``) ``regular`` may hold 1 + 2G values
+        (r0, w_lambda per group, v_lambda per group), as libFM's -regular with -meta."""
         self.cfg = config_default()
         if method not in ("mcmc", "vb", "vb_online", "als") or order not in ("sbpmf", "libfm"):
             raise ValueError("method must be mcmc, als or vb (order sbpmf or libfm)")
@@ -285,7 +316,9 @@ class FMLearnSBPMF:
         else:
             self.cfg.method = METHOD_LIBFM_MCMC if order == "libfm" else METHOD_MCMC
         self.cfg.libfm_dim = (1 if k0 else 0) | (2 if k1 else 0)
-        self.cfg.reg0, self.cfg.regw, self.cfg.regv = (float(x) for x in regular)
+        self._regular, self._groups = regular, None
+        if np.ndim(regular) == 0 or len(regular) <= 3:  # the 1 + 2G form waits for set_groups
+            self.cfg.reg0, self.cfg.regw, self.cfg.regv = parse_regular(regular)[:3]
         self.cfg.vb_batches = vb_batches
         self.cfg.num_factor = num_factor
         self.cfg.num_iter = num_iter
@@ -331,7 +364,44 @@ class FMLearnSBPMF:
         if rc != SBMF_OK:
             raise SBMFError(rc, lib.sbmf_last_error(self.ctx).decode())
 
+    def set_groups(self, group):
+        """libFM's -meta: group[a] is the attribute group of attribute a, for every a < num_attribute
+        (the largest attribute id over train and test + 2; for triples user u is attribute u and
+        item i attribute num_users + i).  libFM's MCMC / ALS learners then draw w_mu, w_lambda,
+        v_mu, v_lambda per group.  Call before set_data; an empty list drops the groups.  Triples
+        given groups run through the general learner (fm_info() / fm() then work)."""
+        g = _u32(group).ravel()
+        self._groups = g if len(g) else None
+        if self.ctx is not None:
+            self._send_groups()
+
+    def _send_groups(self):
+        g = self._groups
+        G = int(g.max()) + 1 if g is not None else 1
+        r0, rw, rv, gw, gv = parse_regular(self._regular, G)
+        if self.ctx is None:  # the context is created with reg0 (the per-group values go to it below)
+            self.cfg.reg0, self.cfg.regw, self.cfg.regv = r0, rw, rv
+            self.init()
+        self._check(lib.sbmf_set_attr_groups(self.ctx, len(g) if g is not None else 0,
+                                             _ptr(g, C.c_uint32) if g is not None else None))
+        if gw is not None:
+            gw, gv = _f64(gw), _f64(gv)
+            self._check(lib.sbmf_set_group_regular(self.ctx, G, _ptr(gw, C.c_double), _ptr(gv, C.c_double)))
+
+    def fm_groups(self):
+        """sbmf_get_fm_groups: {"G", "cnt" [G], "w_lambda" [G], "w_mu" [G], "v_lambda" [G, K], "v_mu" [G, K]}."""
+        G, K = C.c_uint32(), self.cfg.num_factor
+        self._check(lib.sbmf_get_fm_groups(self.ctx, C.byref(G), None, None, None, None, None))
+        n = G.value
+        cnt, wl, wm = np.zeros(n, np.uint32), np.zeros(n), np.zeros(n)
+        vl, vm = np.zeros((n, K)), np.zeros((n, K))
+        self._check(lib.sbmf_get_fm_groups(self.ctx, C.byref(G), _ptr(cnt, C.c_uint32), _ptr(wl, C.c_double),
+                                           _ptr(wm, C.c_double), _ptr(vl, C.c_double), _ptr(vm, C.c_double)))
+        return {"G": n, "cnt": cnt, "w_lambda": wl, "w_mu": wm, "v_lambda": vl, "v_mu": vm}
+
     def set_data(self, train, test=None, num_users=0, num_items=0):
+        if self._groups is not None or not (np.ndim(self._regular) == 0 or len(self._regular) <= 3):
+            self._send_groups()
         self.init()
         self._train, self._test = train, test
         if isinstance(train, Cases):  # libFM order / ALS: cases with any number of features

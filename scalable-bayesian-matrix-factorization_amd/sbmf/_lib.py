@@ -139,6 +139,11 @@ SIGNATURES = {
     "sbmf_set_test_cases": (C.c_int, [C.c_void_p, C.POINTER(CasesC)]),
     "sbmf_get_fm": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
     "sbmf_fm_info": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_U32]),
+    "sbmf_set_attr_groups": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32]),
+    "sbmf_set_group_regular": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_get_fm_groups": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_F64, _P_F64, _P_F64, _P_F64]),
+    "sbmf_load_libfm_meta": (C.c_int, [C.c_char_p, C.c_uint32, _P_U32, _P_U32]),
+    "sbmf_test_fm_group_sums": (C.c_int, [C.c_void_p, _P_F64]),
     "sbmf_partition_rows": (C.c_int, [_P_U32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "sbmf_ref_stream": (C.c_int, [C.c_uint32, C.c_int, C.c_double, C.c_uint64, _P_F64]),
     "sbmf_philox_normals": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P_F64]),
