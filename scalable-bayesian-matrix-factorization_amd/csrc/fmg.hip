@@ -8,26 +8,24 @@
 // a case (sbmf_fm_ranges), so the scatter has no collisions and needs no atomics; every sum
 // has a fixed order, so a rerun is bit-identical.  Contraction is off in the arithmetic that
 // restates libFM's expressions: the reference is compiled without fused multiply-adds.
+// What does not depend on how the cases are stored is fm_dev.h, shared with fmm.hip (listed
+// there); this file keeps the {e, q} cache walk, the group lookup of the draw's prior, k_fmg_q
+// and fg_pred.
 #include <hip/hip_runtime.h>
 
 #include "fmg.h"
 
+#define FM_DEV_CONTRACT off  // the draw without fused multiply-adds, as the rest of this file
+#include "fm_dev.h"
+
 namespace sbmf {
 namespace {
 
-__device__ __forceinline__ double wsum(double x) {  // xor butterfly: bit-identical in every lane
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
-// The row's draw from its sums m = sum h e, s2 = sum h^2 (fm_learn_mcmc.h:680-710, :793-824);
-// keep: a non-finite draw restores the old value (the reference returns before the update).
-// GR: the prior is the row's group's (lm[grp[at]], one small load per row); else the launch's scalars.
+// The row's draw (fm_draw) under its prior.  GR: the row's group's (lm[grp[at]], one small load
+// per row); else the launch's scalars.
 template <int MODE, bool GR>
 __device__ __forceinline__ double fmg_draw(const FGPassArgs& a, uint32_t at, double old, double m, double s2,
                                            bool& keep) {
-#pragma clang fp contract(off)
     double lambda = a.lambda, mu = a.mu;
     if constexpr (GR) {
         const uint32_t g = a.grp_bytes == 1   ? static_cast<const uint8_t*>(a.grp)[at]
@@ -37,20 +35,7 @@ __device__ __forceinline__ double fmg_draw(const FGPassArgs& a, uint32_t at, dou
         lambda = t.x;
         mu = t.y;
     }
-    if constexpr (MODE == 1) m -= old * s2;
-    s2 = 1.0 / (lambda + a.alpha * s2);
-    m = -s2 * (a.alpha * m - mu * lambda);
-    double nv;
-    if (isnan(s2) || isinf(s2)) {
-        nv = 0.0;
-    } else if (a.do_sample) {  // ran_gaussian(mean, stdev), random.h:166-172
-        const double sd = sqrt(s2);
-        nv = (sd == 0.0 || isnan(sd)) ? m : m + sd * a.z[(size_t)at * a.zs + a.zoff];
-    } else {
-        nv = m;
-    }
-    keep = isnan(nv) || isinf(nv);
-    return keep ? old : nv;
+    return fm_draw<MODE>(a, lambda, mu, at, old, m, s2, keep);
 }
 
 // MODE 0: draw_w (fm_learn_mcmc.h:670-719); MODE 1: draw_v (:780-835).  NT threads per row; a
@@ -63,19 +48,7 @@ __device__ __forceinline__ void fmg_pass_body(const FGPassArgs& a) {
     const int sub = threadIdx.x / NT, lt = threadIdx.x % NT;
     const uint32_t ri = blockIdx.x * RPB + sub;
     if (NT == 64 && ri >= a.nrows) return;  // a whole wave: no block barriers on this path
-    uint32_t row, beg, n, di;
-    if (a.chunks) {
-        const uint4 ck = a.chunks[ri];
-        row = ck.x;
-        beg = ck.y;
-        n = ck.z;
-        di = ck.w;
-    } else {
-        row = a.rows[ri];
-        beg = a.aptr[row];
-        n = a.aptr[row + 1] - beg;
-        di = 0;
-    }
+    const auto [row, beg, n, di] = fm_row<false>(a, &FGPassArgs::aptr, ri);
     const int xm = a.xmode;
     const double4 dl = xm == 2 ? a.delta[di] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double old = xm == 2 ? dl.x : a.own[row];
@@ -123,24 +96,9 @@ __device__ __forceinline__ void fmg_pass_body(const FGPassArgs& a) {
         }
     }
     if (xm != 2) {
-        m = wsum(m);
-        s2 = wsum(s2);
-        if constexpr (NWR > 1) {  // waves of the row meet in LDS, summed in wave order
-            __shared__ double red[2][NWR];
-            const int w = lt >> 6;
-            if ((lt & 63) == 0) {
-                red[0][w] = m;
-                red[1][w] = s2;
-            }
-            __syncthreads();
-            m = 0.0;
-            s2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NWR; ++k) {
-                m += red[0][k];
-                s2 += red[1][k];
-            }
-        }
+        const double2 ms = row_sum<NWR>(lt, m, s2);
+        m = ms.x;
+        s2 = ms.y;
     }
     if (xm == 1) {  // the chunk's share of its row's sums
         if (lt == 0) a.sums[ri] = make_double2(m, s2);
@@ -194,24 +152,15 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmg_gpass(FGPassArgs a)
     fmg_pass_body<MODE, NT, true>(a);
 }
 
-// long rows in chunks: one thread per long row, chunk sums in chunk order, then the draw
+// long rows in chunks: the draw per long row
 template <int MODE, bool GR>
 __device__ __forceinline__ void fmg_chunk_draw_body(const FGPassArgs& a, const uint32_t* __restrict__ rows,
                                                     const uint32_t* __restrict__ cfirst, uint32_t nlong,
                                                     const double2* __restrict__ csums, double4* __restrict__ delta) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nlong) return;
-    double m = 0.0, s2 = 0.0;
-    for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; ++c) {
-        m += csums[c].x;
-        s2 += csums[c].y;
-    }
-    const uint32_t at = rows[i];
-    const double old = a.own[at];
-    bool keep;
-    const double nv = fmg_draw<MODE, GR>(a, at, old, m, s2, keep);
-    a.own[at] = nv;
-    delta[i] = make_double4(old, nv, keep ? 1.0 : 0.0, 0.0);
+    fm_chunk_draw_body(a.own, 0, rows, cfirst, nlong, csums, delta, nullptr, nullptr,
+                       [&](uint32_t at, double old, double m, double s2, bool& keep) {
+                           return fmg_draw<MODE, GR>(a, at, old, m, s2, keep);
+                       });
 }
 template <int MODE>
 __global__ __launch_bounds__(256) void k_fmg_chunk_draw(FGPassArgs a, const uint32_t* __restrict__ rows,
@@ -239,33 +188,11 @@ __global__ __launch_bounds__(256) void k_fmg_q(const uint32_t* __restrict__ cptr
 
 __global__ __launch_bounds__(256) void k_fmg_esums(const double2* __restrict__ eq, uint64_t n, double w0,
                                                    double* __restrict__ part) {
-    const uint64_t b0 = (uint64_t)blockIdx.x * 1024;
-    double s = 0.0, d = 0.0;
-    for (int k = 0; k < 4; ++k) {
-        const uint64_t q = b0 + k * 256 + threadIdx.x;
-        if (q < n) {
-            const double v = eq[q].x;
-            s += v * v;
-            d += v - w0;
-        }
-    }
-    s = wsum(s);
-    d = wsum(d);
-    __shared__ double red[2][4];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = s;
-        red[1][threadIdx.x >> 6] = d;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        part[2 * blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    }
+    fm_esums_body(eq, n, w0, part);
 }
 
 __global__ __launch_bounds__(256) void k_fmg_shift(double2* __restrict__ eq, uint64_t n, double d) {
-    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q < n) eq[q].x -= d;
+    fm_shift_body(eq, n, d);
 }
 
 // prediction of case c: e = sum_f 1/2 q_f^2 with q_f over the case's entries in ascending
@@ -293,54 +220,15 @@ __device__ __forceinline__ double fg_pred(const FGPredictArgs& a, uint64_t c) {
     return e;
 }
 
-__device__ __forceinline__ double clampd(double p, double lo, double hi) {
-    p = p < hi ? p : hi;     // std::min(max_target, p)
-    return p > lo ? p : lo;  // std::max(min_target, p)
-}
-
-__device__ __forceinline__ double block_sum(double s, double* red) {  // 256 threads, fixed order
-    s = wsum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(256) void k_fmg_predict_train(FGPredictArgs a, double2* __restrict__ eq,
                                                            double* __restrict__ part) {
-    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    double se = 0.0;
-    if (c < a.n) {
-        const double pr = fg_pred(a, c);
-        const double err = clampd(pr, a.lo, a.hi) - a.y[c];
-        se = err * err;
-        eq[c] = make_double2(pr - a.y[c], 0.0);
-    }
-    __shared__ double red[4];
-    se = block_sum(se, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = se;
+    fm_train_frame(a, a.n, a.y, part, [&](uint64_t c) { return fg_pred(a, c); },
+                   [&](uint64_t c, double r) { eq[c] = make_double2(r, 0.0); });
 }
 
 __global__ __launch_bounds__(256) void k_fmg_predict_test(FGPredictArgs a, double it1, double* __restrict__ pthis,
                                                           double* __restrict__ sum_all, double* __restrict__ part) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    double sa = 0.0, st = 0.0;
-    if (t < a.n) {
-        const double pr = fg_pred(a, t);
-        pthis[t] = pr;
-        const double s = sum_all[t] + clampd(pr, a.lo, a.hi);
-        sum_all[t] = s;
-        const double ea = clampd(s * (1.0 / it1), a.lo, a.hi) - a.y[t];  // _evaluate: pred * normalizer
-        const double et = clampd(pr * 1.0, a.lo, a.hi) - a.y[t];
-        sa = ea * ea;
-        st = et * et;
-    }
-    __shared__ double red[2][4];
-    sa = block_sum(sa, red[0]);
-    st = block_sum(st, red[1]);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = sa;
-        part[2 * blockIdx.x + 1] = st;
-    }
+    fm_test_frame(a, a.n, a.y, it1, pthis, sum_all, part, [&](uint64_t t) { return fg_pred(a, t); });
 }
 
 template <int MODE, bool GR>
@@ -348,92 +236,35 @@ hipError_t launch_pass(const FGPassArgs& a, int tpr, hipStream_t st) {
     if (a.nrows == 0) return hipSuccess;
     if (a.xmode != 0 && !a.chunks) return hipErrorInvalidValue;
     if (GR && (!a.lm || (a.grp_bytes != 1 && a.grp_bytes != 2 && a.grp_bytes != 4))) return hipErrorInvalidValue;
-    switch (tpr) {
-        case 64:
-            if (GR)
-                k_fmg_gpass<MODE, 64><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
-            else
-                k_fmg_pass<MODE, 64><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
-            break;
-        case 256:
-            if (GR)
-                k_fmg_gpass<MODE, 256><<<a.nrows, 256, 0, st>>>(a);
-            else
-                k_fmg_pass<MODE, 256><<<a.nrows, 256, 0, st>>>(a);
-            break;
-        case 1024:
-            if (GR)
-                k_fmg_gpass<MODE, 1024><<<a.nrows, 1024, 0, st>>>(a);
-            else
-                k_fmg_pass<MODE, 1024><<<a.nrows, 1024, 0, st>>>(a);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return fm_launch_rows(tpr, a.nrows, [&](auto nt, dim3 grid, dim3 block) {
+        constexpr int NT = decltype(nt)::value;
+        if (GR)
+            k_fmg_gpass<MODE, NT><<<grid, block, 0, st>>>(a);
+        else
+            k_fmg_pass<MODE, NT><<<grid, block, 0, st>>>(a);
+    });
 }
 
-// The grouped form of k_fmm_hsums (fmm.hip): block (c, g) runs the two chains of group g of
-// column c.  The workgroup stages 1024-value chunks of the group's values and their squared
-// deviations in LDS (double-buffered, 32 KiB: four groups' workgroups share a CU's 160 KiB where
-// k_fmm_hsums' 64 KiB admit two); lane 0 runs the gm chain and lane 1 the m chain.  A contiguous
-// group reads its range, any other gathers through its ascending member list.
+// The grouped form of k_fmm_hsums (fmm.hip): block (c, g) runs the two chains (fm_chains_body) of
+// group g of column c in 1024-value chunks (32 KiB of LDS: four groups' workgroups share a CU's
+// 160 KiB where k_fmm_hsums' 64 KiB admit two).  A contiguous group reads its range, any other
+// gathers through its ascending member list.
 __global__ __launch_bounds__(256) void k_fmg_gsums(const double* __restrict__ v, const double* __restrict__ w,
                                                    uint32_t p, uint32_t K, uint32_t G,
                                                    const uint32_t* __restrict__ gptr, const uint32_t* __restrict__ gidx,
                                                    const uint32_t* __restrict__ gfirst, const double2* __restrict__ mg,
                                                    double2* __restrict__ out) {
-#pragma clang fp contract(off)
-    constexpr uint32_t CH = 1024;
-    __shared__ __align__(16) double xs[2][CH];
-    __shared__ __align__(16) double ds[2][CH];
     const uint32_t c = blockIdx.x, g = blockIdx.y;
     const double* __restrict__ x = c < K ? v + (size_t)c * p : w;
     const uint32_t b0 = gptr[g], cnt = gptr[g + 1] - b0, first = gfirst[g];
-    const double2 in = mg[(size_t)c * G + g];
-    const double mu = in.x;
-    double acc = threadIdx.x == 0 ? in.y : 0.0;  // lane 0: gm, lane 1: m
-    const uint32_t nch = (cnt + CH - 1) / CH;
-    auto stage = [&](uint32_t ch, int b) {
-        for (uint32_t i = threadIdx.x; i < CH; i += 256) {
-            const uint32_t q = ch * CH + i;
-            double t = 0.0;
-            if (q < cnt) {
-                const uint32_t at = first != 0xffffffffu ? first + q : gidx[b0 + q];
-                if (at < p) t = x[at];
-            }
-            const double d = t - mu;
-            xs[b][i] = t;
-            ds[b][i] = d * d;
-        }
-    };
-    stage(0, 0);
-    __syncthreads();
-    for (uint32_t ch = 0; ch < nch; ++ch) {
-        const int b = ch & 1;
-        if (ch + 1 < nch) stage(ch + 1, b ^ 1);
-        if (threadIdx.x < 2) {
-            const double* __restrict__ src = threadIdx.x == 0 ? ds[b] : xs[b];
-            const uint32_t n = min(CH, cnt - ch * CH);
-            uint32_t j = 0;
-            for (; j + 32 <= n; j += 32) {
-                double2 t[16];  // 16-byte LDS reads, all issued before the first add
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = reinterpret_cast<const double2*>(src + j)[u];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    acc = acc + t[u].x;
-                    acc = acc + t[u].y;
-                }
-            }
-            for (; j < n; ++j) acc = acc + src[j];
-        }
-        __syncthreads();
-    }
-    __shared__ double res[2];
-    if (threadIdx.x < 2) res[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[(size_t)c * G + g] = make_double2(res[0], res[1]);
+    const size_t cg = (size_t)c * G + g;
+    const double2 in = mg[cg];
+    fm_chains_body<1024, uint32_t>(cnt, &in, out, cg, [&](uint32_t q) {
+        const uint32_t at = first != 0xffffffffu ? first + q : gidx[b0 + q];
+        double t = 0.0;
+        if (at < p) t = x[at];
+        return t;
+    });
 }
 
 }  // namespace

@@ -9,39 +9,19 @@
 // the case's two factor values) is not stored: the user pass rebuilds it as
 // v_u + v_i, the item pass as (v_u_old + v_i) - (v_u_old - v_u_new), the
 // same operations fm_learn_mcmc.h:385-409 and :826-834 apply to it.
+// What does not depend on how the cases are stored (reductions, row decode, the draw, the chunk
+// draw, the residual sums, the column chains, the prediction frames, the launch switch) is
+// fm_dev.h, shared with fmg.hip; this file keeps the case loop with its pending-update records
+// and rebuilt q, the several-rank item draw, the transpose and fm_pred.
 #include <hip/hip_runtime.h>
 
 #include "fmm.h"
 
+#define FM_DEV_CONTRACT fast  // HIP's default: the draw as these kernels' pinned bits were recorded
+#include "fm_dev.h"
+
 namespace sbmf {
 namespace {
-
-__device__ __forceinline__ double wsum(double x) {  // xor butterfly: bit-identical in every lane
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
-// The row's draw from its sums m = sum h e, s2 = sum h^2 (fm_learn_mcmc.h:700-719,
-// :815-835); keep: a non-finite draw restores the old value (the reference returns).
-template <int MODE>
-__device__ __forceinline__ double fmm_draw(const FMPassArgs& a, uint32_t at, double old, double m, double s2,
-                                           bool& keep) {
-    if constexpr (MODE == 1) m -= old * s2;
-    s2 = 1.0 / (a.lambda + a.alpha * s2);
-    m = -s2 * (a.alpha * m - a.mu * a.lambda);
-    double nv;
-    if (isnan(s2) || isinf(s2)) {
-        nv = 0.0;
-    } else if (a.do_sample) {  // ran_gaussian(mean, stdev), random.h:166-172
-        const double sd = sqrt(s2);
-        nv = (sd == 0.0 || isnan(sd)) ? m : m + sd * a.z[(size_t)at * a.zs + a.zoff];
-    } else {
-        nv = m;
-    }
-    keep = isnan(nv) || isinf(nv);
-    return keep ? old : nv;
-}
 
 // MODE 0: draw_w (fm_learn_mcmc.h:670-719); MODE 1: draw_v (:780-835).
 // NT threads per row; a 256-thread block holds 256 / NT rows (NT <= 256) or
@@ -53,19 +33,7 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmm_pass(FMPassArgs a) 
     const int sub = threadIdx.x / NT, lt = threadIdx.x % NT;
     const uint32_t ri = blockIdx.x * RPB + sub;
     if (NT == 64 && ri >= a.nrows) return;  // a whole wave: no block barriers on this path
-    uint32_t row, beg, n, di;  // di: the row's slot in sums / delta
-    if (a.chunks) {            // a chunk of a long row (one rank)
-        const uint4 ck = a.chunks[ri];
-        row = ck.x;
-        beg = ck.y;
-        n = ck.z;
-        di = ck.w;
-    } else {
-        row = a.rows[ri];
-        beg = a.ptr[row];
-        n = a.ptr[row + 1] - beg;
-        di = row;
-    }
+    const auto [row, beg, n, di] = fm_row<true>(a, &FMPassArgs::ptr, ri);  // di: the row's slot in delta
     const uint32_t at = a.a0 + row;
     const int xm = a.xmode;
     const double4 dl = xm == 2 ? a.delta[di] : make_double4(0.0, 0.0, 0.0, 0.0);
@@ -173,24 +141,9 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmm_pass(FMPassArgs a) 
             s2 += h * h;
         }
     }
-    m = wsum(m);
-    s2 = wsum(s2);
-    if constexpr (NWR > 1) {  // waves of the row meet in LDS, summed in wave order
-        __shared__ double red[2][NWR];
-        const int w = lt >> 6;
-        if ((lt & 63) == 0) {
-            red[0][w] = m;
-            red[1][w] = s2;
-        }
-        __syncthreads();
-        m = 0.0;
-        s2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < NWR; ++k) {
-            m += red[0][k];
-            s2 += red[1][k];
-        }
-    }
+    const double2 ms = row_sum<NWR>(lt, m, s2);
+    m = ms.x;
+    s2 = ms.y;
     if (xm == 1) {  // several ranks: this rank's share of the row's sums (chunks: the chunk's)
         if (lt == 0) a.sums[a.chunks ? ri : row] = make_double2(m, s2);
         return;
@@ -201,7 +154,7 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmm_pass(FMPassArgs a) 
         nv = dl.y;
         keep = dl.z != 0.0;
     } else {
-        nv = fmm_draw<MODE>(a, at, old, m, s2, keep);
+        nv = fm_draw<MODE>(a, a.lambda, a.mu, at, old, m, s2, keep);
         if (lt == 0) {
             a.own[at] = nv;
             if constexpr (IP) a.rec[at] = make_double2(old, nv);  // nv == old when kept
@@ -246,90 +199,22 @@ __global__ __launch_bounds__(NT > 256 ? NT : 256) void k_fmm_pass(FMPassArgs a) 
 
 __global__ __launch_bounds__(256) void k_fmm_esums(const double* __restrict__ e, uint64_t n, double w0,
                                                    double* __restrict__ part) {
-    const uint64_t b0 = (uint64_t)blockIdx.x * 1024;
-    double s = 0.0, d = 0.0;
-    for (int k = 0; k < 4; ++k) {
-        const uint64_t q = b0 + k * 256 + threadIdx.x;
-        if (q < n) {
-            const double v = e[q];
-            s += v * v;
-            d += v - w0;
-        }
-    }
-    s = wsum(s);
-    d = wsum(d);
-    __shared__ double red[2][4];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = s;
-        red[1][threadIdx.x >> 6] = d;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        part[2 * blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    }
+    fm_esums_body(e, n, w0, part);
 }
 
 // The sums the hyperparameter draws of fm_learn_mcmc.h:951-1089 take over one column of the
-// model (v column f for blockIdx f < K, w for blockIdx K), in the host loop's order: one
-// sequential chain each, gm from its initial value (beta_0 (mu - mu_0)^2 + gamma_0, host)
-// adding (x_i - mu)^2 for i = 0..p-1, and m from 0 adding x_i -- so the result is the host
-// loop's, bit for bit (no contraction).  The whole workgroup stages 2048-value chunks of the
-// column and their squared deviations in LDS (double-buffered); lane 0 runs the gm chain and
-// lane 1 the m chain, side by side in one instruction stream.
+// model (v column f for blockIdx f < K, w for blockIdx K): fm_chains_body over all p attributes
+// in 2048-value chunks (64 KiB of LDS).
 __global__ __launch_bounds__(256) void k_fmm_hsums(const double* __restrict__ v, const double* __restrict__ w,
                                                    uint32_t p, uint32_t K, const double2* __restrict__ mg,
                                                    double2* __restrict__ out) {
-#pragma clang fp contract(off)
-    constexpr uint32_t CH = 2048;
-    __shared__ __align__(16) double xs[2][CH];
-    __shared__ __align__(16) double ds[2][CH];
     const uint32_t c = blockIdx.x;
     const double* __restrict__ x = c < K ? v + (size_t)c * p : w;
-    const double mu = mg[c].x;
-    double acc = threadIdx.x == 0 ? mg[c].y : 0.0;  // lane 0: gm, lane 1: m
-    const uint32_t nch = (p + CH - 1) / CH;
-    auto stage = [&](uint32_t ch, int b) {
-        for (uint32_t i = threadIdx.x; i < CH; i += 256) {
-            const uint64_t q = (uint64_t)ch * CH + i;
-            const double t = q < p ? x[q] : 0.0;
-            const double d = t - mu;
-            xs[b][i] = t;
-            ds[b][i] = d * d;
-        }
-    };
-    stage(0, 0);
-    __syncthreads();
-    for (uint32_t ch = 0; ch < nch; ++ch) {
-        const int b = ch & 1;
-        if (ch + 1 < nch) stage(ch + 1, b ^ 1);
-        if (threadIdx.x < 2) {
-            const double* __restrict__ src = threadIdx.x == 0 ? ds[b] : xs[b];
-            const uint32_t n = min(CH, p - ch * CH);
-            uint32_t j = 0;
-            for (; j + 32 <= n; j += 32) {
-                double2 t[16];  // 16-byte LDS reads, all issued before the first add
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = reinterpret_cast<const double2*>(src + j)[u];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    acc = acc + t[u].x;
-                    acc = acc + t[u].y;
-                }
-            }
-            for (; j < n; ++j) acc = acc + src[j];
-        }
-        __syncthreads();
-    }
-    __shared__ double res[2];
-    if (threadIdx.x < 2) res[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[c] = make_double2(res[0], res[1]);
+    fm_chains_body<2048, uint64_t>(p, &mg[c], out, c, [&](uint64_t q) { return x[q]; });
 }
 
 __global__ __launch_bounds__(256) void k_fmm_shift(double* __restrict__ e, uint64_t n, double d) {
-    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q < n) e[q] -= d;
+    fm_shift_body(e, n, d);
 }
 
 __global__ __launch_bounds__(256) void k_fmm_transpose(const double* __restrict__ v, double* __restrict__ vT,
@@ -384,33 +269,12 @@ __device__ __forceinline__ double fm_pred(const FMPredictArgs& a, uint32_t p0, u
     return e;
 }
 
-__device__ __forceinline__ double clampd(double p, double lo, double hi) {
-    p = p < hi ? p : hi;  // std::min(max_target, p)
-    return p > lo ? p : lo;  // std::max(min_target, p)
-}
-
-__device__ __forceinline__ double block_sum(double s, double* red) {  // 256 threads, fixed order
-    s = wsum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(256) void k_fmm_predict_train(FMPredictArgs a, const uint32_t* __restrict__ own_u,
                                                            const uint32_t* __restrict__ part_u,
                                                            const float* __restrict__ y, uint64_t n,
                                                            double* __restrict__ e, double* __restrict__ part) {
-    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    double se = 0.0;
-    if (q < n) {
-        const double pr = fm_pred(a, own_u[q], a.I + part_u[q]);
-        const double err = clampd(pr, a.lo, a.hi) - y[q];
-        se = err * err;
-        e[q] = pr - y[q];
-    }
-    __shared__ double red[4];
-    se = block_sum(se, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = se;
+    fm_train_frame(a, n, y, part, [&](uint64_t q) { return fm_pred(a, own_u[q], a.I + part_u[q]); },
+                   [&](uint64_t q, double r) { e[q] = r; });
 }
 
 __global__ __launch_bounds__(256) void k_fmm_predict_test(FMPredictArgs a, const uint32_t* __restrict__ su,
@@ -418,25 +282,8 @@ __global__ __launch_bounds__(256) void k_fmm_predict_test(FMPredictArgs a, const
                                                           const float* __restrict__ y, uint64_t n, double it1,
                                                           double* __restrict__ pthis, double* __restrict__ sum_all,
                                                           double* __restrict__ part) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    double sa = 0.0, st = 0.0;
-    if (t < n) {
-        const double pr = fm_pred(a, su[t], a.I + si[t]);
-        pthis[t] = pr;
-        const double s = sum_all[t] + clampd(pr, a.lo, a.hi);
-        sum_all[t] = s;
-        const double ea = clampd(s * (1.0 / it1), a.lo, a.hi) - y[t];  // _evaluate: pred * normalizer
-        const double et = clampd(pr * 1.0, a.lo, a.hi) - y[t];
-        sa = ea * ea;
-        st = et * et;
-    }
-    __shared__ double red[2][4];
-    sa = block_sum(sa, red[0]);
-    st = block_sum(st, red[1]);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = sa;
-        part[2 * blockIdx.x + 1] = st;
-    }
+    fm_test_frame(a, n, y, it1, pthis, sum_all, part,
+                  [&](uint64_t t) { return fm_pred(a, su[t], a.I + si[t]); });
 }
 
 // several ranks: one thread per item row, sums added in rank order, then the draw
@@ -453,52 +300,28 @@ __global__ __launch_bounds__(256) void k_fmm_item(FMPassArgs a, const double2* _
     const uint32_t at = a.a0 + row;
     const double old = a.own[at];
     bool keep;
-    const double nv = fmm_draw<MODE>(a, at, old, m, s2, keep);
+    const double nv = fm_draw<MODE>(a, a.lambda, a.mu, at, old, m, s2, keep);
     a.own[at] = nv;
     delta[row] = make_double4(old, nv, keep ? 1.0 : 0.0, 0.0);
 }
 
-// one rank, long rows in chunks: one thread per long row, chunk sums in chunk order
+// one rank, long rows in chunks: the draw per long row
 template <int MODE>
 __global__ __launch_bounds__(256) void k_fmm_chunk_draw(FMPassArgs a, const uint32_t* __restrict__ rows,
                                                         const uint32_t* __restrict__ cfirst, uint32_t nlong,
                                                         const double2* __restrict__ csums, double4* __restrict__ delta,
                                                         double2* __restrict__ qq) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nlong) return;
-    double m = 0.0, s2 = 0.0;
-    for (uint32_t c = cfirst[i]; c < cfirst[i + 1]; ++c) {
-        m += csums[c].x;
-        s2 += csums[c].y;
-    }
-    const uint32_t at = a.a0 + rows[i];
-    const double old = a.own[at];
-    bool keep;
-    const double nv = fmm_draw<MODE>(a, at, old, m, s2, keep);
-    a.own[at] = nv;
-    if (a.rec) {
-        qq[i] = a.rec[at];
-        a.rec[at] = make_double2(old, nv);  // nv == old when kept
-    }
-    delta[i] = make_double4(old, nv, keep ? 1.0 : 0.0, 0.0);
+    fm_chunk_draw_body(a.own, a.a0, rows, cfirst, nlong, csums, delta, a.rec, qq,
+                       [&](uint32_t at, double old, double m, double s2, bool& keep) {
+                           return fm_draw<MODE>(a, a.lambda, a.mu, at, old, m, s2, keep);
+                       });
 }
 
 template <int MODE, bool IP>
 hipError_t launch_pass_ip(const FMPassArgs& a, int tpr, hipStream_t st) {
-    switch (tpr) {
-        case 64:
-            k_fmm_pass<MODE, 64, IP><<<(a.nrows + 3) / 4, 256, 0, st>>>(a);
-            break;
-        case 256:
-            k_fmm_pass<MODE, 256, IP><<<a.nrows, 256, 0, st>>>(a);
-            break;
-        case 1024:
-            k_fmm_pass<MODE, 1024, IP><<<a.nrows, 1024, 0, st>>>(a);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return fm_launch_rows(tpr, a.nrows, [&](auto nt, dim3 grid, dim3 block) {
+        k_fmm_pass<MODE, decltype(nt)::value, IP><<<grid, block, 0, st>>>(a);
+    });
 }
 template <int MODE>
 hipError_t launch_pass(const FMPassArgs& a, int tpr, hipStream_t st) {

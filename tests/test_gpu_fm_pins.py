@@ -8,10 +8,13 @@ oracle within 1e-9: a changed Philox tag, a swapped host draw or a lost launch p
 does not pass here.
 
 The fixture was recorded from the build before the host chain of the two learners was merged,
-through the Python interface alone.  To record it again, run this file on an MI355X with
-SBMF_FM_PINS_RECORD=1 in the environment: every case then writes its entry instead of
-comparing.  Only a change that means to alter the learners' arithmetic, their launch counts or
-the order of their draws may do so, and says so; recording twice must give the same file.
+through the Python interface alone; the grouped cases (groups5-*: k_fmg_gpass, k_fmg_gchunk_draw and
+k_fmg_gsums inside a chain, fm_groups() in place of hyper(), which refuses G > 1) from the build
+before the two kernel files took their shared code from csrc/fm_dev.h.  To record it again, run
+this file on an MI355X with SBMF_FM_PINS_RECORD=1 in the environment: every case then writes its
+entry instead of comparing.  Only a change that means to alter the learners' arithmetic, their
+launch counts or the order of their draws may do so, and says so; recording twice must give the
+same file.
 
 num_factor = 0 (libFM's -dim 1,1,0) is refused by sbmf_create, so those cases pin the refusal."""
 import hashlib
@@ -22,6 +25,7 @@ import numpy as np
 import pytest
 
 import fm_cases
+import fm_groups
 from conftest import GOLD, gpu_available
 from sbmf import Data, FMLearnSBPMF, SBMFError
 from test_gpu_multirank import _run_ranks
@@ -43,7 +47,12 @@ def _hyper(L):
     return np.concatenate([hy["sigma_u"], hy["mu_u"], hy["sigma_v"], hy["mu_v"], [hy["tau"]]])
 
 
-def _pins(L, general):
+def _group_hyper(L):
+    fg = L.fm_groups()
+    return np.concatenate([np.ravel(fg[k]) for k in ("cnt", "w_lambda", "w_mu", "v_lambda", "v_mu")])
+
+
+def _pins(L, general, grouped=False):
     rec = {k: _digest([h[k] for h in L.history]) for k in ("rmse_train", "rmse_avg", "rmse_this", "tau")}
     rec["predict"] = _digest(L.predict() if L._test is not None else np.zeros(0))
     if general:
@@ -52,7 +61,10 @@ def _pins(L, general):
     else:
         (U, V), (bu, bv, b0) = L.factors(), L.biases()
         rec.update(U=_digest(U), V=_digest(V), bu=_digest(bu), bv=_digest(bv), b0=_digest([b0]))
-    rec["hyper"] = _digest(_hyper(L))
+    if grouped:  # sbmf_get_hyper refuses G > 1: the group getter's arrays stand in its place
+        rec["fm_groups"] = _digest(_group_hyper(L))
+    else:
+        rec["hyper"] = _digest(_hyper(L))
     rec["n_launch"] = int(L.timing().n_launch)
     return rec
 
@@ -80,10 +92,12 @@ def _learner(method="mcmc", rng="ref", dim=(1, 1, 4), regular=(0.0, 0.0, 0.0), s
                         regular=regular, init_stdev=0.1)
 
 
-def _run(train, test, general, iters=3, stop_then_one=False, **kw):
+def _run(train, test, general, iters=3, stop_then_one=False, group=None, **kw):
     """The pins of one run: `iters` iterations, or (stop_then_one) five iterations whose callback
     stops after the second, then one more learn(1) -- the break and the carried iteration count."""
     L = _learner(**kw)
+    if group is not None:
+        L.set_groups(group)
     try:
         L.set_data(train, test)
     except SBMFError as e:
@@ -96,7 +110,7 @@ def _run(train, test, general, iters=3, stop_then_one=False, **kw):
     else:
         L.learn(sweeps=iters)
     assert len(L.history) == 3
-    rec = _pins(L, general)
+    rec = _pins(L, general, group is not None)
     L.close()
     return rec
 
@@ -158,6 +172,24 @@ def test_general_edge_set(case, monkeypatch):
         monkeypatch.setenv("SBMF_FMM_CHUNK", "64")
     tr, te = fm_cases.edge_set()
     _check("general/edge/" + case, _run(tr, te, True, seed=2, **kw))
+
+
+# five group ids, one empty, two interleaved over the rows at the bin and chunk edges
+# (fm_groups.edge_groups()); the ALS case's -regular is w0's, then the five groups' for w, then for v
+GROUPS5 = {"mcmc-ref-long256-chunk64": dict(env=True), "mcmc-philox": dict(rng="philox"),
+           "als": dict(method="als", regular=(0.25, 0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 4.0, 5.0, 6.0, 7.0))}
+
+
+@pytest.mark.parametrize("case", sorted(GROUPS5))
+def test_general_edge_set_groups(case, monkeypatch):
+    """k_fmg_gpass, k_fmg_gchunk_draw (the chunked case) and k_fmg_gsums inside a chain."""
+    assert gpu_available()
+    kw = dict(GROUPS5[case])
+    if kw.pop("env", False):
+        monkeypatch.setenv("SBMF_FMM_LONG", "256")
+        monkeypatch.setenv("SBMF_FMM_CHUNK", "64")
+    tr, te = fm_cases.edge_set()
+    _check("general/edge/groups5-" + case, _run(tr, te, True, seed=2, group=fm_groups.edge_groups(), **kw))
 
 
 def test_general_small_cases_als():
