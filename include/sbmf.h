@@ -86,6 +86,8 @@ enum sbmf_quirks { SBMF_QUIRKS_FINAL = 0, SBMF_QUIRKS_SBPMF2 = 1, SBMF_QUIRKS_NO
  * are all-gathered and added in rank order, so every rank draws the same items
  * and the chain equals one rank's up to the rounding of that sum. */
 enum sbmf_method { SBMF_METHOD_MCMC = 0, SBMF_METHOD_VB = 1, SBMF_METHOD_LIBFM_MCMC = 2, SBMF_METHOD_ALS = 3 };
+/* libFM's -task (sbmf_config::task) */
+enum sbmf_task { SBMF_TASK_REGRESSION = 0, SBMF_TASK_CLASSIFICATION = 1 };
 
 /* Arithmetic type of factors, residuals and reductions on the GPU.  F64 is
  * the reference's (all-double) arithmetic. */
@@ -187,6 +189,10 @@ typedef struct sbmf_config {
                                  running.  A stop the callback asks for takes effect after sweep
                                  s+1.  0 (default): each sweep is reported with the device idle
                                  after it                                                         */
+    uint32_t task;            /* enum sbmf_task: SBMF_TASK_REGRESSION (default) | SBMF_TASK_CLASSIFICATION
+                                 (libFM's -task c, a probit model: targets <= 0 become -1, the others
+                                 +1, libfm.cpp:454-455; min / max target play no part).  LIBFM_MCMC and
+                                 ALS only; any other method with it is SBMF_E_ARG                  */
 } sbmf_config;
 
 /* Per-sweep report passed to the run callback. */
@@ -205,6 +211,13 @@ typedef struct sbmf_sweep_info {
                                   previous sweep, beside its test evaluation, and is not in here
                                   (sbmf_timing.ms_hyper of the previous sweep holds it)        */
     double ms_eval;            /* device time of the test evaluation, ms                      */
+    /* SBMF_TASK_CLASSIFICATION (the rmse_* above are then NaN; these are NaN in regression; tau
+       stays alpha): */
+    double acc_train;          /* share of the train cases this sweep's model classifies right  */
+    double acc_avg;            /* test accuracy of the running-mean probability (libFM's "Test=",
+                                  fm_learn_mcmc_simultaneous.h:327-338); NaN if no test set      */
+    double acc_this;           /* test accuracy of this sweep's probabilities alone (:383-401)   */
+    double ll_this;            /* their mean -log10 likelihood, clipped to [0.01, 0.99]          */
 } sbmf_sweep_info;
 
 /* Return non-zero to stop the run early. */
@@ -243,7 +256,9 @@ int sbmf_run(sbmf_ctx* ctx, uint32_t sweeps, sbmf_sweep_cb cb, void* user);
 
 /* --- results ------------------------------------------------------------------------------- */
 /* Averaged clamped test prediction (sum / collected sweeps; libfm -out,
- * libfm.cpp:629-634).  out: [n_test]. */
+ * libfm.cpp:629-634).  out: [n_test].  SBMF_TASK_CLASSIFICATION: the probability of the
+ * positive class (MCMC: the mean over the iterations; ALS: the last iteration's), clipped to
+ * [0, 1] (fm_learn_mcmc.h:355-379). */
 int sbmf_predict(sbmf_ctx* ctx, double* out);
 /* Factors as row-major doubles: U [num_users][K], V [num_items][K]. Either may be NULL. */
 int sbmf_get_factors(sbmf_ctx* ctx, double* U, double* V);
@@ -662,6 +677,15 @@ int sbmf_test_device_usage(int device, sbmf_device_usage* out);
  * K (v column c, then w) and the groups g, as the next iteration's hyperparameter
  * draws would read them. */
 int sbmf_test_fm_group_sums(sbmf_ctx* ctx, double* out);
+/* The latent targets of libFM's classification alone: out[i] = a normal with mean mean[i] and
+ * variance 1 truncated to (0, inf) where sign[i] >= 0 and to (-inf, 0) otherwise
+ * (fm_learn_mcmc_simultaneous.h:197-218).  mode 0 (device): the Philox draw of the train frames
+ * for the key (seed, it, index[i]) -- index: the cases' places in the train file, null for i --,
+ * on `device`.  mode 1 (host, needs no GPU): the reference's ran_left_tgaussian /
+ * ran_right_tgaussian restated over its own stream seeded with `seed`, consumed in the order of
+ * i (`it`, `index` and `device` unused). */
+int sbmf_test_tgauss(int mode, int device, uint64_t seed, uint32_t it, uint64_t n, const double* mean,
+                     const int32_t* sign, const uint32_t* index, double* out);
 
 #ifdef __cplusplus
 }

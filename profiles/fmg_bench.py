@@ -12,6 +12,11 @@ A setting followed by a digit runs the same cases with that many attribute group
 else, c4 = users | items | the 7-value field | the 24-value field with the trailing attribute,
 d4 = users | items | the two one-hot fields | the tags.  (a has no grouped form: the
 two-attribute kernels keep one group.)
+--task c runs the same settings as binary classification (libFM's -task c): the
+targets binarised at the train set's median rating (+1 above it, else -1), --method mcmc (Philox
+draws of the latent targets in the train frame) or als (their expected values); a run then
+reports the test accuracy in place of the RMSE.  The evaluate step (transpose, train and test
+frames, their sums) is ms_eval_events, the draws' sweep ms_sweep_events.
 Per run: ms per iteration from a host clock around --steps iterations ending in a device
 synchronise, after --warmup iterations, and the mean of the iterations' HIP-event times
 (sweep + evaluation); launches per iteration and the ranges from fm_info.  One JSON line on
@@ -67,6 +72,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--settings", default="a,b,c,d")
+    ap.add_argument("--task", default="r", choices=["r", "c"])
+    ap.add_argument("--method", default="mcmc", choices=["mcmc", "als"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--bench-this", nargs="*", default=None)
     ap.add_argument("--bench-parent", nargs="*", default=None)
@@ -75,6 +82,11 @@ def main():
     from sbmf import Data, FMLearnSBPMF, synth
     train, test, dims = synth.generate(args.shape)
     I, J = int(dims[0]), int(dims[1])
+    if args.task == "c":  # binarised at the median of the train ratings
+        med = float(np.median(train[2]))
+        train = (train[0], train[1], np.where(train[2] > med, 1.0, -1.0))
+        test = (test[0], test[1], np.where(test[2] > med, 1.0, -1.0))
+        print("# task c: median %g, %.4f of the train cases positive" % (med, float(np.mean(train[2] > 0))), flush=True)
     sets = {}
 
     def groups(setting, p):
@@ -110,7 +122,11 @@ def main():
         if name == "b":
             os.environ["SBMF_FMM_GENERAL"] = "1"
         try:
-            L = FMLearnSBPMF(num_factor=args.K, seed=2015, rng="philox", method="mcmc", order="libfm", init_stdev=0.1)
+            kw = {"task": "c"} if args.task == "c" else {}  # (a tree without the task runs regression)
+            if args.method == "als":
+                kw["regular"] = (0.0, 1.0, 10.0)
+            L = FMLearnSBPMF(num_factor=args.K, seed=2015, rng="philox", method=args.method, order="libfm",
+                             init_stdev=0.1, **kw)
             if len(name) > 1:
                 L.set_groups(groups(name, int(max(train[0].max(), test[0].max())) + int(max(train[1].max(), test[1].max())) + 3
                                     if setting == "b" else max(tr.num_attr, te.num_attr) + 1))
@@ -125,7 +141,13 @@ def main():
         device_sync()
         res = {"ms_per_iter_host": 1e3 * (time.perf_counter() - t0) / args.steps,
                "ms_per_iter_events": float(np.mean([h["ms_sweep"] + h["ms_eval"] for h in L.history[n0:]])),
-               "rmse_test": L.history[-1]["rmse_avg"], "launches_per_iter": int(L.timing().n_launch)}
+               "ms_sweep_events": float(np.mean([h["ms_sweep"] for h in L.history[n0:]])),
+               "ms_eval_events": float(np.mean([h["ms_eval"] for h in L.history[n0:]])),
+               "launches_per_iter": int(L.timing().n_launch)}
+        if args.task == "c":
+            res.update(acc_test=L.history[-1]["acc_avg"], acc_train=L.history[-1]["acc_train"])
+        else:
+            res["rmse_test"] = L.history[-1]["rmse_avg"]
         if setting != "a":
             info = L.fm_info()
             res.update(num_attr=info["num_attr"], nranges=info["nranges"])
@@ -141,8 +163,11 @@ def main():
     for _ in range(args.reps):
         for s in names:
             runs[s].append(run(s))
-    out = {"what": "libFM MCMC, %s K=%d f64 philox: (a) two-attribute learner, (b) general learner on the same cases, "
-                   "(c) + one-hot fields of 7 and 24 values, (d) + a 5-tag multi-hot field" % (args.shape, args.K),
+    out = {"what": "libFM %s%s, %s K=%d f64 philox: (a) two-attribute learner, (b) general learner on the same cases, "
+                   "(c) + one-hot fields of 7 and 24 values, (d) + a 5-tag multi-hot field"
+                   % (args.method.upper(), " classification (targets binarised at the median)" if args.task == "c" else "",
+                      args.shape, args.K),
+           "task": args.task, "method": args.method,
            "num_users": I, "num_items": J, "n_train": int(len(train[0])), "steps": args.steps, "warmup": args.warmup,
            "runs": runs,
            "bench_py_this_commit": bench_lines(args.bench_this), "bench_py_parent_commit": bench_lines(args.bench_parent)}

@@ -3,8 +3,9 @@
 // how the cases are stored.  The fixed-order reductions, the decode of a launch index into a row
 // or a chunk, the row's draw with the reference's rules for non-finite values, the chunk draw of
 // long rows, the residual sums and shift, the staged column chains of the hyperparameter draws,
-// the train / test prediction frames -- all device code -- and one host helper, the threads-per-row
-// launch switch (fm_launch_rows), which sits here because it names the kernels' NT instantiations.
+// the train / test prediction frames of regression and of classification (fm_target.h) -- all
+// device code -- and one host helper, the threads-per-row launch switch (fm_launch_rows), which
+// sits here because it names the kernels' NT instantiations.
 //
 // Included by those two files only, which define FM_DEV_CONTRACT first: the state of `#pragma
 // clang fp contract` in the row's draw.  fmg.hip restates libFM's expressions without fused
@@ -15,6 +16,9 @@
 
 #include <cstdint>
 #include <type_traits>
+
+#include "fm_target.h"
+#include "rng.h"
 
 #ifndef FM_DEV_CONTRACT
 #error "define FM_DEV_CONTRACT (off or fast) before including fm_dev.h"
@@ -283,6 +287,141 @@ __device__ __forceinline__ void fm_test_frame(const A& a, uint64_t n, const floa
         part[2 * blockIdx.x] = sa;
         part[2 * blockIdx.x + 1] = st;
     }
+}
+
+// ---- the classification frames (-task c, fm_target.h): the same one pass per case, the targets
+// y in {-1, +1}.  Counts are integers, summed exactly (fm_count_sums_body).
+__device__ __forceinline__ uint32_t block_count(bool hit, uint32_t* red) {  // 256 threads
+    const uint32_t w = (uint32_t)__popcll(__ballot(hit));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// the reference's vote (fm_learn_mcmc_simultaneous.h:193, :333, :389)
+__device__ __forceinline__ bool fm_vote(double p, float y) { return (p >= 0.5 && y > 0.0f) || (p < 0.5 && y < 0.0f); }
+
+// ran_left_tgaussian(left) (random.h:72-102) from the counter-based stream of (seed, it, row).
+// Both loops are bounded: 64 tries, then the truncation point (fm_target.h has the odds).
+__device__ __forceinline__ double fm_left_tgauss(uint64_t seed, uint32_t it, uint32_t row, double left) {
+#pragma clang fp contract(off)
+    if (left <= 0.0) {  // naive rejection, two normals per Philox block
+        for (uint32_t t = 0; t < 32; ++t) {
+            double z0, z1;
+            philox_normal_pair(seed, row, it, TAG_FMC_TARGET, t, z0, z1);
+            if (!(z0 < left)) return z0;
+            if (!(z1 < left)) return z1;
+        }
+        return left;
+    }
+    // Robert's translated exponential: ran_exp and ran_uniform of one Philox block per try
+    const double alpha_star = 0.5 * (left + sqrt(left * left + 4.0));
+    for (uint32_t t = 0; t < 64; ++t) {
+        double u0, u1;
+        philox_uniform_pair(seed, row, it, TAG_FMC_TARGET, t, u0, u1);
+        const double z = -log(u0) / alpha_star + left;  // u0 in (0, 1]: the reference's 1 - ran_uniform()
+        double d = z - alpha_star;
+        d = exp(-(d * d) / 2);
+        if (u1 < d) return z;
+    }
+    return left;
+}
+
+// the latent target of a case with prediction mu and label y (fm_learn_mcmc_simultaneous.h:197-218)
+template <int TM>
+__device__ __forceinline__ double fm_target(const FMTargetArgs& ta, uint64_t c, double mu, float y) {
+#pragma clang fp contract(off)
+    if constexpr (TM == FM_TGT_ALS) {
+        const double phi_minus_mu = exp(-mu * mu / 2.0) / sqrt(3.141 * 2);
+        const double Phi_minus_mu = ref_cdf_gaussian(-mu);
+        return y >= 0.0f ? mu + phi_minus_mu / (1 - Phi_minus_mu) : mu - phi_minus_mu / Phi_minus_mu;
+    } else {
+        const uint32_t row = ta.fidx ? ta.fidx[c] : (uint32_t)c;
+        const double lim = (0.0 - mu) / 1.0;  // (left - mean) / stdev, (right - mean) / stdev
+        return y >= 0.0f ? mu + 1.0 * fm_left_tgauss(ta.seed, ta.it, row, lim)
+                         : mu + 1.0 * -fm_left_tgauss(ta.seed, ta.it, row, -lim);
+    }
+}
+
+// Train: p = cdf_gaussian(pred) votes, store(c, pred - latent target); ta.cnt[b] = the block's
+// correct votes.  FM_TGT_HOST: store(c, pred) and ta.yhat[c] = pred, the targets follow from the host.
+template <int TM, class Pred, class Store>
+__device__ __forceinline__ void fm_class_train_frame(const FMTargetArgs& ta, uint64_t n, const float* y, Pred pred,
+                                                     Store store) {
+#pragma clang fp contract(off)
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool hit = false;
+    if (c < n) {
+        const double pr = pred(c);
+        const float yc = y[c];
+        hit = fm_vote(ref_cdf_gaussian(pr), yc);
+        if constexpr (TM == FM_TGT_HOST) {
+            ta.yhat[c] = pr;
+            store(c, pr);
+        } else {
+            store(c, pr - fm_target<TM>(ta, c, pr, yc));
+        }
+    }
+    __shared__ uint32_t red[4];
+    const uint32_t k = block_count(hit, red);
+    if (threadIdx.x == 0) ta.cnt[blockIdx.x] = k;
+}
+
+// Test: pthis[t] = p = cdf_gaussian(pred), sum_all[t] += p (no clamp); cnt[2b] = the block's
+// correct votes of the running mean sum_all / it1, cnt[2b + 1] of p; ll[b] = the block's sum of
+// -(m log10 q + (1 - m) log10(1 - q)), q = p clipped to [0.01, 0.99], m = (y + 1) / 2
+// (_evaluate_class_map's first loop and _evaluate_class, :327-338, :383-401)
+template <class Pred>
+__device__ __forceinline__ void fm_class_test_frame(uint64_t n, const float* y, double it1, double* pthis,
+                                                    double* sum_all, uint32_t* cnt, double* ll, Pred pred) {
+#pragma clang fp contract(off)
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool ha = false, ht = false;
+    double l = 0.0;
+    if (t < n) {
+        const double p = ref_cdf_gaussian(pred(t));
+        pthis[t] = p;
+        const double s = sum_all[t] + p;
+        sum_all[t] = s;
+        const float yt = y[t];
+        ha = fm_vote(s * (1.0 / it1), yt);
+        ht = fm_vote(p * 1.0, yt);
+        const double m = (yt + 1.0) * 0.5;
+        double pll = p;
+        if (pll > 0.99) pll = 0.99;
+        if (pll < 0.01) pll = 0.01;
+        l = -(m * log10(pll) + (1 - m) * log10(1 - pll));
+    }
+    __shared__ uint32_t red[2][4];
+    __shared__ double redl[4];
+    const uint32_t ka = block_count(ha, red[0]), kt = block_count(ht, red[1]);
+    l = block_sum(l, redl);
+    if (threadIdx.x == 0) {
+        cnt[2 * blockIdx.x] = ka;
+        cnt[2 * blockIdx.x + 1] = kt;
+        ll[blockIdx.x] = l;
+    }
+}
+
+// out[w] = sum_b part[b * width + w], exact (64-bit integers); one 256-thread block per column w
+__device__ __forceinline__ void fm_count_sums_body(const uint32_t* __restrict__ part, uint32_t nb, uint32_t width,
+                                                   unsigned long long* __restrict__ out) {
+    const uint32_t w = blockIdx.x;
+    unsigned long long s = 0;
+    for (uint32_t b = threadIdx.x; b < nb; b += 256) s += part[(size_t)b * width + w];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    __shared__ unsigned long long red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[w] = red[0] + red[1] + red[2] + red[3];
+}
+
+// e[q] -= t[q]: the host's targets (FM_TGT_HOST)
+template <class T>
+__device__ __forceinline__ void fm_sub_body(T* __restrict__ e, uint64_t n, const double* __restrict__ t) {
+    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < n) fm_residual(e[q]) -= t[q];
 }
 
 // ---- host: a pass over nrows rows with tpr threads each.  launch(NT, grid, block) starts the

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "fmg.h"
 #include "fmm.h"
@@ -262,6 +263,22 @@ void FMChain::run(uint32_t iters, sbmf_sweep_cb cb, void* user) {
             sweep_draws(ps);
         }
         HIPCHK(hipEventRecord(ev[1], st));
+        if (classify()) {
+            sbmf_sweep_info info{};
+            evaluate_class(info);
+            float ms0 = 0.f, ms1 = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms0, ev[0], ev[1]));
+            HIPCHK(hipEventElapsedTime(&ms1, ev[1], ev[2]));
+            info.sweep = it;
+            info.collected = 1;
+            info.rmse_train = info.rmse_avg = info.rmse_this = NAN;
+            info.tau = alpha;
+            info.ms_sweep = ms0;
+            info.ms_eval = ms1;
+            ++it;
+            if (cb && cb(&info, user)) break;
+            continue;
+        }
         // ---- predict train and test, evaluate (fm_learn_mcmc_simultaneous.h:134-245)
         predict_train();
         train_sum(res + 2);
@@ -284,12 +301,65 @@ void FMChain::run(uint32_t iters, sbmf_sweep_cb cb, void* user) {
         info.rmse_train = std::sqrt(h[0] / (double)N);
         info.rmse_avg = T ? std::sqrt(h[1] / (double)T) : NAN;
         info.rmse_this = T ? std::sqrt(h[2] / (double)T) : NAN;
+        info.acc_train = info.acc_avg = info.acc_this = info.ll_this = NAN;
         info.tau = alpha;
         info.ms_sweep = ms0;
         info.ms_eval = ms1;
         ++it;
         if (cb && cb(&info, user)) break;
     }
+}
+
+// Classification's evaluate step (fm_learn_mcmc_simultaneous.h:176-222, :262-275): the test frame,
+// then the train frame, which also forms the new latent targets; the counts summed as integers.
+// Records ev[2] and waits for the stream.
+void FMChain::evaluate_class(sbmf_sweep_info& info) {
+    HIPCHK(fmm_transpose(d_v.as<double>(), d_vT.as<double>(), K, Kp, p, st));
+    ++n_launch;
+    const uint32_t nbt = (uint32_t)((T + 255) / 256), nb = (uint32_t)((N + 255) / 256);
+    unsigned long long* cres = d_cres.as<unsigned long long>();
+    double* ll = d_tpart.as<double>();
+    uint32_t* tcnt = reinterpret_cast<uint32_t*>(ll + nbt);
+    if (T) {
+        class_test((double)(it + 1), tcnt, ll);
+        HIPCHK(fm_count_sums(tcnt, nbt, 2, cres + 1, st));
+        HIPCHK(launch_sum_cols(ll, nbt, 1, reinterpret_cast<double*>(cres + 3), st));
+        n_launch += 3;
+    }
+    FMTargetArgs ta{};
+    ta.mode = !do_sample ? FM_TGT_ALS : cfg.rng_mode == SBMF_RNG_REFERENCE ? FM_TGT_HOST : FM_TGT_PHILOX;
+    ta.seed = cfg.seed;
+    ta.it = it;
+    ta.yhat = d_tgt.as<double>();
+    ta.cnt = d_part.as<uint32_t>();
+    class_train(ta);
+    HIPCHK(fm_count_sums(ta.cnt, nb, 1, cres, st));
+    n_launch += 2;
+    if (ta.mode == FM_TGT_HOST) {
+        // the reference's stream, in the train file's order (this mode is for parity: a round
+        // trip of N doubles and a serial host loop per iteration)
+        std::vector<double> t(N);
+        HIPCHK(hipMemcpyAsync(t.data(), d_tgt.p, N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint64_t c = 0; c < N; ++c) {
+            const uint64_t q = pos_of_file.empty() ? c : pos_of_file[c];
+            t[q] = y_pos[q] >= 0.0f ? ran_left_tgaussian(grand, 0.0, t[q], 1.0) : ran_right_tgaussian(grand, 0.0, t[q], 1.0);
+        }
+        HIPCHK(hipMemcpyAsync(d_tgt.p, t.data(), N * sizeof(double), hipMemcpyHostToDevice, st));
+        sub_targets(d_tgt.as<double>());
+        ++n_launch;
+        HIPCHK(hipStreamSynchronize(st));  // t is a local
+    }
+    HIPCHK(hipEventRecord(ev[2], st));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h, cres, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double llsum;
+    std::memcpy(&llsum, &h[3], sizeof llsum);
+    info.acc_train = (double)h[0] / (double)N;
+    info.acc_avg = T ? (double)h[1] / (double)T : NAN;
+    info.acc_this = T ? (double)h[2] / (double)T : NAN;
+    info.ll_this = T ? llsum / (double)T : NAN;
 }
 
 void FMChain::setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr, uint64_t n, uint64_t nl, uint64_t nt,
@@ -326,6 +396,20 @@ void FMChain::setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr,
     d_part.alloc((std::max<uint64_t>((nl + 255) / 256, 2 * ((nl + 1023) / 1024)) + 2) * sizeof(double));
     d_tpart.alloc((2 * ((nt + 255) / 256) + 2) * sizeof(double));
     d_res.alloc(8 * sizeof(double));
+    if (classify()) {
+        // {train votes, running-mean test votes, this sweep's test votes} as 64-bit counts, then the ll sum
+        d_cres.alloc(4 * sizeof(double));
+        HIPCHK(hipMemsetAsync(d_cres.p, 0, d_cres.bytes, st));
+        if (y_pos.empty()) y_pos.assign(y, y + n);
+        if (!file_of_pos.empty()) {
+            pos_of_file.resize(n);
+            for (uint64_t q = 0; q < n; ++q) pos_of_file[file_of_pos[q]] = (uint32_t)q;
+        }
+        if (do_sample && c.rng_mode == SBMF_RNG_REFERENCE)
+            d_tgt.alloc(n * sizeof(double));
+        else if (do_sample && !file_of_pos.empty())
+            upload(d_fidx, file_of_pos, st);
+    }
     // the groups a learner set before this call (grp: [p], G = max + 1; empty: one group)
     if (grp.empty()) G = 1;
     cnt.assign(G, 0);
@@ -376,15 +460,16 @@ void FMChain::setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr,
 }
 
 // fm_learn_mcmc::predict (:357-380): the running sum over the iterations run
-// (MCMC) or the last prediction (ALS), clamped to the train range
+// (MCMC) or the last prediction (ALS), clamped to the train range -- in classification the
+// probabilities, clipped to [0, 1]
 void FMChain::predict_out(double* out) {
     HIPCHK(hipStreamSynchronize(st));
     if (!T) return;
     HIPCHK(hipMemcpy(out, (do_sample ? d_sum : d_pthis).p, T * sizeof(double), hipMemcpyDeviceToHost));
     for (uint64_t t = 0; t < T; ++t) {
         double o = do_sample ? out[t] / std::max(1u, it) : out[t];
-        o = std::min(hi, o);
-        o = std::max(lo, o);
+        o = std::min(classify() ? 1.0 : hi, o);
+        o = std::max(classify() ? 0.0 : lo, o);
         out[t] = o;
     }
 }

@@ -17,6 +17,13 @@
 // and v passes ahead of the launches.  Philox mode fills those normals on the device.  ALS
 // (do_sample = do_multilevel = 0) draws nothing: alpha = 1, the draws take their posterior means.
 //
+// Classification (cfg.task, libFM's -task c; fm_target.h): the targets are -1 / +1, each train
+// case keeps a latent Gaussian target on its label's side of 0, and step 5 becomes: predict,
+// p = cdf_gaussian(prediction), count the correct votes, form the case's new latent target (ALS:
+// its expected value; MCMC: a truncated-normal draw) and store e = prediction - latent target --
+// one launch over the train cases -- and report accuracies in place of RMSEs.  Steps 1-4 do not
+// look at targets: they are the same draws in the same order.
+//
 // FMChain owns the model, the hyperparameter state, the generator and every buffer the two
 // layouts share; a learner derives from it and supplies what depends on how the cases are
 // stored, through the hooks below.
@@ -28,6 +35,7 @@
 
 #include "../../include/sbmf.h"
 #include "common.h"
+#include "fm_target.h"
 #include "rng.h"
 
 namespace sbmf {
@@ -87,6 +95,12 @@ struct FMChain {
     virtual void gather_train_sum(double* h) {}
     // the test set: d_pthis, d_sum and d_tpart as fmm_predict_test writes them (the chain counts the launch)
     virtual void predict_test(double it1) = 0;
+    // classification: the train frame (the chain fills ta but fidx, which is the learner's;
+    // one launch), the test frame (d_pthis, d_sum; cnt[2b], cnt[2b + 1], ll[b] per 256-case block)
+    // and e[q] -= t[q] over the train cases by position
+    virtual void class_train(FMTargetArgs ta) = 0;
+    virtual void class_test(double it1, uint32_t* cnt, double* ll) = 0;
+    virtual void sub_targets(const double* t) = 0;
 
     // ---- what the chain does
     // the shared set-up, last in a learner's create (its data uploaded): the flags, the target
@@ -94,6 +108,14 @@ struct FMChain {
     // model in either RNG mode and the starting predictions
     void setup(const sbmf_config& c, hipStream_t stream, uint32_t num_attr, uint64_t n, uint64_t nl, uint64_t nt,
                const float* y);
+    bool classify() const { return cfg.task == SBMF_TASK_CLASSIFICATION; }
+    // classification: a learner that keeps its train cases in another order than the train file's
+    // sets, before setup, file_of_pos[q] = the file index of the case at position q (empty: the
+    // position) and y_pos[q] = its -1 / +1 target.  The Philox draws are keyed by the file index
+    // and the reference stream is consumed in file order, so no draw depends on the layout.
+    std::vector<uint32_t> file_of_pos, pos_of_file;  // pos_of_file: the inverse, built by setup
+    std::vector<float> y_pos;
+    DBuf d_fidx, d_tgt, d_cres;
     void predict_train();
     void run(uint32_t iters, sbmf_sweep_cb cb, void* user);
     void predict_out(double* out);                 // the -out predictions
@@ -112,6 +134,7 @@ protected:
     void upload_priors(bool vcols);
 
 private:
+    void evaluate_class(sbmf_sweep_info& info);
     void ensure_group_lists();
     void launch_hsums();
     template <class R>

@@ -130,6 +130,14 @@ struct FGLearner : FMChain {
         HIPCHK(fmg_predict_test(predict_args(false), it1, d_pthis.as<double>(), d_sum.as<double>(), d_tpart.as<double>(),
                                 st));
     }
+    void class_train(FMTargetArgs ta) override {
+        ta.fidx = d_fidx.as<uint32_t>();
+        HIPCHK(fmg_class_train(predict_args(true), ta, d_eq.as<double2>(), st));
+    }
+    void class_test(double it1, uint32_t* cnt, double* ll) override {
+        HIPCHK(fmg_class_test(predict_args(false), it1, d_pthis.as<double>(), d_sum.as<double>(), cnt, ll, st));
+    }
+    void sub_targets(const double* t) override { HIPCHK(fmg_sub_targets(d_eq.as<double2>(), N, t, st)); }
     void residual_sums(double* s) override {
         double* res = d_res.as<double>();
         HIPCHK(fmg_esums(d_eq.as<double2>(), N, w0, d_part.as<double>(), st));
@@ -168,7 +176,7 @@ struct FGLearner : FMChain {
 // line per case.  The order of the cases is a labelling: no draw depends on it.
 struct OrderedCases {
     std::vector<uint64_t> ptr;
-    std::vector<uint32_t> attr;
+    std::vector<uint32_t> attr, order;  // order[k]: the file index of the case at position k
     std::vector<float> x, y;
     bool build(const sbmf_cases& in, sbmf_cases& out) {
         auto key = [&](uint64_t c) { return in.ptr[c + 1] > in.ptr[c] ? in.attr[in.ptr[c]] : in.num_attr; };
@@ -178,7 +186,7 @@ struct OrderedCases {
         std::vector<uint64_t> pos((size_t)in.num_attr + 2, 0);
         for (uint64_t c = 0; c < in.n; ++c) pos[key(c) + 1]++;
         for (size_t k = 0; k + 1 < pos.size(); ++k) pos[k + 1] += pos[k];
-        std::vector<uint32_t> order(in.n);
+        order.resize(in.n);
         for (uint64_t c = 0; c < in.n; ++c) order[pos[key(c)]++] = (uint32_t)c;
         ptr.assign(in.n + 1, 0);
         attr.resize(in.nnz);
@@ -203,15 +211,28 @@ struct OrderedCases {
     }
 };
 
-FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& tr_file, const sbmf_cases& te, hipStream_t st,
+FMChain* fmg_create(const sbmf_config& c, const sbmf_cases& tr_file, const sbmf_cases& te_in, hipStream_t st,
                     const FMGroups* groups) {
     if (tr_file.n == 0) fail(SBMF_E_STATE, "no training cases");
-    if (tr_file.n >= 0xffffffffull || te.n >= 0xffffffffull || tr_file.nnz >= 0xffffffffull || te.nnz >= 0xffffffffull)
+    if (tr_file.n >= 0xffffffffull || te_in.n >= 0xffffffffull || tr_file.nnz >= 0xffffffffull || te_in.nnz >= 0xffffffffull)
         fail(SBMF_E_ARG, "more than 2^32-1 cases or features are not supported");
     OrderedCases oc;
     sbmf_cases tr_ordered{};
-    const sbmf_cases& tr = oc.build(tr_file, tr_ordered) ? tr_ordered : tr_file;
+    const sbmf_cases& tr_in = oc.build(tr_file, tr_ordered) ? tr_ordered : tr_file;
+    // classification: the learner's own copy of the targets, <= 0 to -1 and the others to +1 (libfm.cpp:454-455)
+    sbmf_cases tr = tr_in, te = te_in;
+    std::vector<float> ytr, yte;
+    if (c.task == SBMF_TASK_CLASSIFICATION) {
+        auto map = [](const sbmf_cases& cs, std::vector<float>& y) {
+            y.resize(cs.n);
+            for (uint64_t x = 0; x < cs.n; ++x) y[x] = cs.target[x] <= 0.0f ? -1.0f : 1.0f;
+            return y.data();
+        };
+        tr.target = map(tr_in, ytr);
+        te.target = map(te_in, yte);
+    }
     std::unique_ptr<FGLearner> L(new FGLearner());
+    if (c.task == SBMF_TASK_CLASSIFICATION) L->file_of_pos = oc.order;
     // num_all_attribute = max(train, test num_feature) + 1 (libfm.cpp:328)
     if (std::max(tr.num_attr, te.num_attr) >= 0xfffffffeu) fail(SBMF_E_ARG, "attribute id too large");
     const uint32_t p = std::max(tr.num_attr, te.num_attr) + 1;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/sbmf.h"
+#include "fm_target.h"
 
 namespace sbmf {
 
@@ -92,6 +93,15 @@ struct FGPredictArgs {
 hipError_t fmg_predict_train(const FGPredictArgs& a, double2* eq, double* part, hipStream_t st);
 hipError_t fmg_predict_test(const FGPredictArgs& a, double it1, double* pthis, double* sum_all, double* part,
                             hipStream_t st);
+// The classification frames (fm_target.h; y in {-1, +1}).  Train: eq[c] = {pred - latent target, 0}
+// (FM_TGT_HOST: {pred, 0} and ta.yhat[c] = pred), ta.cnt[b] the block's correct votes.  Test:
+// pthis[t] = p = cdf_gaussian(pred), sum_all[t] += p, cnt[2b] / cnt[2b+1] the correct votes of
+// sum_all / it1 and of p, ll[b] the block's -log10 likelihood of p clipped to [0.01, 0.99].
+hipError_t fmg_class_train(const FGPredictArgs& a, const FMTargetArgs& ta, double2* eq, hipStream_t st);
+hipError_t fmg_class_test(const FGPredictArgs& a, double it1, double* pthis, double* sum_all, uint32_t* cnt, double* ll,
+                          hipStream_t st);
+// eq[c].e -= t[c] (FM_TGT_HOST: the host's targets)
+hipError_t fmg_sub_targets(double2* eq, uint64_t n, const double* t, hipStream_t st);
 
 // ---- host learner (fmg.cpp): libFM's chain (FMChain, fmc.h) on this layout, driven by the C ABI in sbmf.cpp
 struct FMChain;

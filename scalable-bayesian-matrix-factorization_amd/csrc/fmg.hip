@@ -231,6 +231,23 @@ __global__ __launch_bounds__(256) void k_fmg_predict_test(FGPredictArgs a, doubl
     fm_test_frame(a, a.n, a.y, it1, pthis, sum_all, part, [&](uint64_t t) { return fg_pred(a, t); });
 }
 
+// the classification frames (fm_dev.h) on this layout; TM: how the latent target is formed
+template <int TM>
+__global__ __launch_bounds__(256) void k_fmg_class_train(FGPredictArgs a, FMTargetArgs ta, double2* __restrict__ eq) {
+    fm_class_train_frame<TM>(ta, a.n, a.y, [&](uint64_t c) { return fg_pred(a, c); },
+                             [&](uint64_t c, double r) { eq[c] = make_double2(r, 0.0); });
+}
+
+__global__ __launch_bounds__(256) void k_fmg_class_test(FGPredictArgs a, double it1, double* __restrict__ pthis,
+                                                        double* __restrict__ sum_all, uint32_t* __restrict__ cnt,
+                                                        double* __restrict__ ll) {
+    fm_class_test_frame(a.n, a.y, it1, pthis, sum_all, cnt, ll, [&](uint64_t t) { return fg_pred(a, t); });
+}
+
+__global__ __launch_bounds__(256) void k_fmg_sub(double2* __restrict__ eq, uint64_t n, const double* __restrict__ t) {
+    fm_sub_body(eq, n, t);
+}
+
 template <int MODE, bool GR>
 hipError_t launch_pass(const FGPassArgs& a, int tpr, hipStream_t st) {
     if (a.nrows == 0) return hipSuccess;
@@ -321,6 +338,33 @@ hipError_t fmg_shift(double2* eq, uint64_t n, double d, hipStream_t st) {
 hipError_t fmg_predict_train(const FGPredictArgs& a, double2* eq, double* part, hipStream_t st) {
     if (a.n == 0) return hipSuccess;
     k_fmg_predict_train<<<(unsigned)((a.n + 255) / 256), 256, 0, st>>>(a, eq, part);
+    return hipGetLastError();
+}
+
+hipError_t fmg_class_train(const FGPredictArgs& a, const FMTargetArgs& ta, double2* eq, hipStream_t st) {
+    if (a.n == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((a.n + 255) / 256);
+    if (ta.mode == FM_TGT_ALS)
+        k_fmg_class_train<FM_TGT_ALS><<<grid, 256, 0, st>>>(a, ta, eq);
+    else if (ta.mode == FM_TGT_PHILOX)
+        k_fmg_class_train<FM_TGT_PHILOX><<<grid, 256, 0, st>>>(a, ta, eq);
+    else if (ta.mode == FM_TGT_HOST && ta.yhat)
+        k_fmg_class_train<FM_TGT_HOST><<<grid, 256, 0, st>>>(a, ta, eq);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t fmg_class_test(const FGPredictArgs& a, double it1, double* pthis, double* sum_all, uint32_t* cnt, double* ll,
+                          hipStream_t st) {
+    if (a.n == 0) return hipSuccess;
+    k_fmg_class_test<<<(unsigned)((a.n + 255) / 256), 256, 0, st>>>(a, it1, pthis, sum_all, cnt, ll);
+    return hipGetLastError();
+}
+
+hipError_t fmg_sub_targets(double2* eq, uint64_t n, const double* t, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    k_fmg_sub<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(eq, n, t);
     return hipGetLastError();
 }
 

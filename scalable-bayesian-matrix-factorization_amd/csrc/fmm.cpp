@@ -186,6 +186,16 @@ struct FMLearner : FMChain {
         HIPCHK(fmm_predict_test(predict_args(), d_su.as<uint32_t>(), d_si.as<uint32_t>(), d_sy.as<float>(), T, it1,
                                 d_pthis.as<double>(), d_sum.as<double>(), d_tpart.as<double>(), st));
     }
+    void class_train(FMTargetArgs ta) override {
+        ta.fidx = d_fidx.as<uint32_t>();
+        HIPCHK(fmm_class_train(predict_args(), ta, d_uown.as<uint32_t>(), d_upart.as<uint32_t>(), d_uy.as<float>(), NL,
+                               d_eu.as<double>(), st));
+    }
+    void class_test(double it1, uint32_t* cnt, double* ll) override {
+        HIPCHK(fmm_class_test(predict_args(), d_su.as<uint32_t>(), d_si.as<uint32_t>(), d_sy.as<float>(), T, it1,
+                              d_pthis.as<double>(), d_sum.as<double>(), cnt, ll, st));
+    }
+    void sub_targets(const double* t) override { HIPCHK(fmm_sub_targets(d_eu.as<double>(), NL, t, st)); }
     void residual_sums(double* s) override {
         double* res = d_res.as<double>();
         if (NL) {
@@ -242,6 +252,11 @@ FMChain* fmm_create(const sbmf_config& c, uint64_t n, const uint32_t* u, const u
     }
     L->I = I;
     L->J = J;
+    const bool classify = c.task == SBMF_TASK_CLASSIFICATION;
+    if (classify && L->R > 1)
+        fail(SBMF_E_STATE, "classification (task = SBMF_TASK_CLASSIFICATION) runs on one rank: the latent targets and "
+                           "the vote counts of the train frame are not exchanged between the user ranges of %d ranks",
+             L->R);
     if (n >= 0xffffffffull) fail(SBMF_E_ARG, "more than 2^32-1 ratings are not supported");
     // libFM attribute layout: user u -> u, item i -> I + i; num_feature = largest id + 1 (Data.h:221),
     // num_all_attribute = max(train, test) + 1 (libfm.cpp:330)
@@ -252,6 +267,9 @@ FMChain* fmm_create(const sbmf_config& c, uint64_t n, const uint32_t* u, const u
     L->RI = p - I;
     // DATA_FLOAT targets (fm_data.h:25)
     std::vector<float> y(r, r + n), ys(tr, tr + nt);
+    if (classify)  // the learner's own copy: <= 0 to -1, the others to +1 (libfm.cpp:454-455)
+        for (std::vector<float>* v : {&y, &ys})
+            for (float& t : *v) t = t <= 0.0f ? -1.0f : 1.0f;
     // several ranks: the user ranges (sbmf_partition_rows over the users' rating counts);
     // a rank keeps the cases of its users only
     L->ubounds.assign(L->R + 1, 0);
@@ -348,6 +366,11 @@ FMChain* fmm_create(const sbmf_config& c, uint64_t n, const uint32_t* u, const u
     }
     L->d_vold.alloc((size_t)std::max(I, 1u) * sizeof(double));
     L->d_rec.alloc((size_t)p * sizeof(double2));
+    if (classify) {  // the residuals are in user order: the file index and the target of each position
+        L->file_of_pos.resize(n);
+        for (uint64_t x = 0; x < n; ++x) L->file_of_pos[upos[x]] = (uint32_t)x;
+        L->y_pos = uy;
+    }
     L->setup(c, st, p, n, nl, nt, y.data());
     return L.release();
 }

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "../../include/sbmf.h"
+#include "fm_target.h"
 
 namespace sbmf {
 
@@ -105,6 +106,23 @@ hipError_t fmm_predict_train(const FMPredictArgs& a, const uint32_t* own_u, cons
                              uint64_t n, double* e, double* part, hipStream_t st);
 hipError_t fmm_predict_test(const FMPredictArgs& a, const uint32_t* su, const uint32_t* si, const float* y,
                             uint64_t n, double it1, double* pthis, double* sum_all, double* part, hipStream_t st);
+// The classification frames (fm_target.h; y in {-1, +1}), cases as for the frames above.  Train:
+// e[q] = pred - latent target (FM_TGT_HOST: pred, and ta.yhat[q] = pred), ta.cnt[b] the block's
+// correct votes.  Test: pthis[t] = p = cdf_gaussian(pred), sum_all[t] += p, cnt[2b] / cnt[2b+1]
+// the correct votes of sum_all / it1 and of p, ll[b] the block's -log10 likelihood of p clipped
+// to [0.01, 0.99].
+hipError_t fmm_class_train(const FMPredictArgs& a, const FMTargetArgs& ta, const uint32_t* own_u, const uint32_t* part_u,
+                           const float* y, uint64_t n, double* e, hipStream_t st);
+hipError_t fmm_class_test(const FMPredictArgs& a, const uint32_t* su, const uint32_t* si, const float* y, uint64_t n,
+                          double it1, double* pthis, double* sum_all, uint32_t* cnt, double* ll, hipStream_t st);
+// e[q] -= t[q] (FM_TGT_HOST: the host's targets)
+hipError_t fmm_sub_targets(double* e, uint64_t n, const double* t, hipStream_t st);
+// both layouts: out[w] = sum_b part[b * width + w] of the frames' block counts, in 64-bit integers
+hipError_t fm_count_sums(const uint32_t* part, uint32_t nb, uint32_t width, unsigned long long* out, hipStream_t st);
+// the Philox draw of FM_TGT_PHILOX alone: out[i] = the latent target of a case with prediction
+// mean[i], label y[i] and train file index fidx[i] (null: i) at (seed, it)
+hipError_t fm_tgauss(uint64_t seed, uint32_t it, uint64_t n, const double* mean, const float* y, const uint32_t* fidx,
+                     double* out, hipStream_t st);
 
 // ---- host learner (fmm.cpp): libFM's chain (FMChain, fmc.h) on this layout, driven by the C ABI in sbmf.cpp
 struct FMChain;

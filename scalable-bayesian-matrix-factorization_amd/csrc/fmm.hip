@@ -286,6 +286,41 @@ __global__ __launch_bounds__(256) void k_fmm_predict_test(FMPredictArgs a, const
                   [&](uint64_t t) { return fm_pred(a, su[t], a.I + si[t]); });
 }
 
+// the classification frames (fm_dev.h) on this layout; TM: how the latent target is formed
+template <int TM>
+__global__ __launch_bounds__(256) void k_fmm_class_train(FMPredictArgs a, FMTargetArgs ta,
+                                                         const uint32_t* __restrict__ own_u,
+                                                         const uint32_t* __restrict__ part_u,
+                                                         const float* __restrict__ y, uint64_t n,
+                                                         double* __restrict__ e) {
+    fm_class_train_frame<TM>(ta, n, y, [&](uint64_t q) { return fm_pred(a, own_u[q], a.I + part_u[q]); },
+                             [&](uint64_t q, double r) { e[q] = r; });
+}
+
+__global__ __launch_bounds__(256) void k_fmm_class_test(FMPredictArgs a, const uint32_t* __restrict__ su,
+                                                        const uint32_t* __restrict__ si, const float* __restrict__ y,
+                                                        uint64_t n, double it1, double* __restrict__ pthis,
+                                                        double* __restrict__ sum_all, uint32_t* __restrict__ cnt,
+                                                        double* __restrict__ ll) {
+    fm_class_test_frame(n, y, it1, pthis, sum_all, cnt, ll, [&](uint64_t t) { return fm_pred(a, su[t], a.I + si[t]); });
+}
+
+__global__ __launch_bounds__(256) void k_fmm_sub(double* __restrict__ e, uint64_t n, const double* __restrict__ t) {
+    fm_sub_body(e, n, t);
+}
+
+__global__ __launch_bounds__(256) void k_fm_count_sums(const uint32_t* __restrict__ part, uint32_t nb, uint32_t width,
+                                                       unsigned long long* __restrict__ out) {
+    fm_count_sums_body(part, nb, width, out);
+}
+
+// the Philox draw alone, on given predictions (sbmf_test_tgauss): case i's key is (seed, it, fidx[i])
+__global__ __launch_bounds__(256) void k_fm_tgauss(FMTargetArgs ta, uint64_t n, const double* __restrict__ mean,
+                                                   const float* __restrict__ y, double* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = fm_target<FM_TGT_PHILOX>(ta, i, mean[i], y[i]);
+}
+
 // several ranks: one thread per item row, sums added in rank order, then the draw
 template <int MODE>
 __global__ __launch_bounds__(256) void k_fmm_item(FMPassArgs a, const double2* __restrict__ recv, int R,
@@ -387,6 +422,52 @@ hipError_t fmm_predict_train(const FMPredictArgs& a, const uint32_t* own_u, cons
                              uint64_t n, double* e, double* part, hipStream_t st) {
     if (n == 0) return hipSuccess;
     k_fmm_predict_train<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, own_u, part_u, y, n, e, part);
+    return hipGetLastError();
+}
+
+hipError_t fmm_class_train(const FMPredictArgs& a, const FMTargetArgs& ta, const uint32_t* own_u, const uint32_t* part_u,
+                           const float* y, uint64_t n, double* e, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (ta.mode == FM_TGT_ALS)
+        k_fmm_class_train<FM_TGT_ALS><<<grid, 256, 0, st>>>(a, ta, own_u, part_u, y, n, e);
+    else if (ta.mode == FM_TGT_PHILOX)
+        k_fmm_class_train<FM_TGT_PHILOX><<<grid, 256, 0, st>>>(a, ta, own_u, part_u, y, n, e);
+    else if (ta.mode == FM_TGT_HOST && ta.yhat)
+        k_fmm_class_train<FM_TGT_HOST><<<grid, 256, 0, st>>>(a, ta, own_u, part_u, y, n, e);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t fmm_class_test(const FMPredictArgs& a, const uint32_t* su, const uint32_t* si, const float* y, uint64_t n,
+                          double it1, double* pthis, double* sum_all, uint32_t* cnt, double* ll, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    k_fmm_class_test<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, su, si, y, n, it1, pthis, sum_all, cnt, ll);
+    return hipGetLastError();
+}
+
+hipError_t fmm_sub_targets(double* e, uint64_t n, const double* t, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    k_fmm_sub<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(e, n, t);
+    return hipGetLastError();
+}
+
+hipError_t fm_count_sums(const uint32_t* part, uint32_t nb, uint32_t width, unsigned long long* out, hipStream_t st) {
+    if (width == 0) return hipSuccess;
+    k_fm_count_sums<<<width, 256, 0, st>>>(part, nb, width, out);
+    return hipGetLastError();
+}
+
+hipError_t fm_tgauss(uint64_t seed, uint32_t it, uint64_t n, const double* mean, const float* y, const uint32_t* fidx,
+                     double* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    FMTargetArgs ta{};
+    ta.mode = FM_TGT_PHILOX;
+    ta.seed = seed;
+    ta.it = it;
+    ta.fidx = fidx;
+    k_fm_tgauss<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(ta, n, mean, y, out);
     return hipGetLastError();
 }
 

@@ -105,6 +105,61 @@ SBMF_HDT double mt_gamma(U& g, double alpha) {
     return small ? (d * v) * boost : d * v;
 }
 
+// The reference's own erf (random.h:47-61: the five-term polynomial, not libm's) and the
+// cdf_gaussian over it (:67-69), in its operation order, without fused multiply-adds on the device.
+SBMF_HDT inline double ref_erf(double x) {
+#pragma clang fp contract(off)
+    double t;
+    if (x >= 0) {
+        t = 1.0 / (1.0 + 0.3275911 * x);
+    } else {
+        t = 1.0 / (1.0 - 0.3275911 * x);
+    }
+    const double result =
+        1.0 - (t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429))))) *
+                  exp(-x * x);
+    return x >= 0 ? result : -result;
+}
+SBMF_HDT inline double ref_cdf_gaussian(double x) {
+#pragma clang fp contract(off)
+    return 0.5 + 0.5 * ref_erf(0.707106781 * x);
+}
+
+// random.h:178-180, :72-114 over a sequential uniform source: the truncated normals of libFM's
+// probit targets.  The loops are the reference's (unbounded): host streams only.
+template <class U>
+double ran_exp(U& g) {
+    return -std::log(1 - g.uniform());
+}
+template <class U>
+double ran_left_tgaussian(U& g, double left) {
+    if (left <= 0.0) {  // naive rejection: acceptance > 0.5
+        double result;
+        do {
+            result = leva_normal(g);
+        } while (result < left);
+        return result;
+    }
+    // Robert: translated exponential
+    const double alpha_star = 0.5 * (left + std::sqrt(left * left + 4.0));
+    double z, d, u;
+    do {
+        z = ran_exp(g) / alpha_star + left;
+        d = z - alpha_star;
+        d = std::exp(-(d * d) / 2);
+        u = g.uniform();
+    } while (!(u < d));
+    return z;
+}
+template <class U>
+double ran_left_tgaussian(U& g, double left, double mean, double stdev) {
+    return mean + stdev * ran_left_tgaussian(g, (left - mean) / stdev);
+}
+template <class U>
+double ran_right_tgaussian(U& g, double right, double mean, double stdev) {
+    return mean + stdev * -ran_left_tgaussian(g, -((right - mean) / stdev));
+}
+
 // ----------------------------------------------------------- Philox4x32-10
 struct P4 {
     uint32_t x[4];
@@ -142,6 +197,9 @@ SBMF_HD P4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uin
 // Stream tags (counter word 2, low byte).
 enum : uint32_t { TAG_USERS = 0, TAG_ITEMS = 1, TAG_HOST = 2, TAG_INIT_U = 3, TAG_INIT_V = 4, TAG_BIAS_U = 5,
                   TAG_BIAS_V = 6, TAG_GUEST = 7 /* fold-in rows (foldin.hip), row = the guest's index */ };
+// (8-10 are the libFM chain's normals and initial model, fmc.cpp.)  The probit targets of libFM's
+// classification, drawn in the train frames (fm_dev.h): row = the case's index in the train file.
+enum : uint32_t { TAG_FMC_TARGET = 11 };
 static const uint32_t PHILOX_SALT = 0x53424d46u;  // "SBMF"
 
 // Two N(0,1) variates (Box-Muller, 53-bit uniforms): normal indices 2*pair
@@ -160,6 +218,16 @@ SBMF_HD void philox_normal_pair(uint64_t seed, uint32_t row, uint32_t sweep, uin
     sincos(th, &sn, &cs);  // one argument reduction for both (the values of sin / cos)
     z0 = rr * cs;
     z1 = rr * sn;
+}
+
+// Two uniforms of the same key: u0 in (0,1], u1 in [0,1)
+SBMF_HD void philox_uniform_pair(uint64_t seed, uint32_t row, uint32_t sweep, uint32_t tag, uint32_t pair, double& u0,
+                                 double& u1) {
+    const P4 o = philox4x32_10(row, sweep, tag | (pair << 8), PHILOX_SALT, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint64_t a = (((uint64_t)o.x[0] << 32) | o.x[1]) >> 11;
+    const uint64_t b = (((uint64_t)o.x[2] << 32) | o.x[3]) >> 11;
+    u0 = (double)(a + 1) * (1.0 / 9007199254740992.0);
+    u1 = (double)b * (1.0 / 9007199254740992.0);
 }
 
 // Host-side sequential uniform stream over Philox (hyperparameter draws in

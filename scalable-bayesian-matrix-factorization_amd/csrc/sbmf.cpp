@@ -249,6 +249,13 @@ int sbmf_create(const sbmf_config* cfg, sbmf_ctx** out) {
     if ((cfg->method == SBMF_METHOD_LIBFM_MCMC || cfg->method == SBMF_METHOD_ALS) && cfg->precision != SBMF_F64)
         sbmf::fail(SBMF_E_ARG, "the libFM MCMC / ALS learner computes in f64 (the reference's double) only");
     if (cfg->libfm_dim > 3) sbmf::fail(SBMF_E_ARG, "bad libfm_dim (bit 0 = w0, bit 1 = w)");
+    if (cfg->task > SBMF_TASK_CLASSIFICATION) sbmf::fail(SBMF_E_ARG, "bad task (0 regression, 1 classification)");
+    if (cfg->task == SBMF_TASK_CLASSIFICATION && cfg->method != SBMF_METHOD_LIBFM_MCMC && cfg->method != SBMF_METHOD_ALS) {
+        static const char* const names[] = {"mcmc (the SBPMF sampler)", "vb (online VB)"};
+        sbmf::fail(SBMF_E_ARG, "classification (task = SBMF_TASK_CLASSIFICATION) is libFM's MCMC / ALS learner's "
+                               "(SBMF_METHOD_LIBFM_MCMC, SBMF_METHOD_ALS); method %s fits real-valued targets only",
+                   names[cfg->method]);
+    }
     {
         // the tune bits with a meaning in this build (include/sbmf.h); a bit of a removed variant
         // is refused, so a value saved for an older build does not silently pick something else
@@ -579,6 +586,49 @@ int sbmf_test_fm_group_sums(sbmf_ctx* ctx, double* out) {
         sbmf::fail(SBMF_E_STATE, "sbmf_test_fm_group_sums: this context does not run the general libFM learner");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     ctx->fm->group_sums(out);
+    API_END(ctx)
+}
+
+int sbmf_test_tgauss(int mode, int device, uint64_t seed, uint32_t it, uint64_t n, const double* mean, const int32_t* sign,
+                     const uint32_t* index, double* out) {
+    sbmf_ctx* ctx = nullptr;
+    API_BEGIN
+    if (n && (!mean || !sign || !out)) sbmf::fail(SBMF_E_ARG, "null argument");
+    if (mode == 1) {  // the host restatement over the reference's stream, consumed in index order
+        sbmf::GlibcRand g((unsigned)seed);
+        for (uint64_t i = 0; i < n; ++i)
+            out[i] = sign[i] >= 0 ? sbmf::ran_left_tgaussian(g, 0.0, mean[i], 1.0)
+                                  : sbmf::ran_right_tgaussian(g, 0.0, mean[i], 1.0);
+    } else if (mode == 0) {
+        if (n >= 0xffffffffull) sbmf::fail(SBMF_E_ARG, "more than 2^32-1 draws");
+        int ndev = 0;
+        const hipError_t derr = hipGetDeviceCount(&ndev);
+        if (derr != hipSuccess || ndev <= 0)
+            sbmf::fail(SBMF_E_DEVICE, "no HIP device available (%s; this library has no CPU fallback)",
+                       derr != hipSuccess ? hipGetErrorString(derr) : "0 devices");
+        if (device < 0 || device >= ndev) sbmf::fail(SBMF_E_DEVICE, "device %d out of range (%d)", device, ndev);
+        HIPCHK(hipSetDevice(device));
+        std::vector<float> y(n);
+        for (uint64_t i = 0; i < n; ++i) y[i] = sign[i] >= 0 ? 1.0f : -1.0f;
+        sbmf::DBuf d_mean, d_y, d_out, d_idx;
+        if (index && n) {
+            d_idx.alloc(n * sizeof(uint32_t));
+            HIPCHK(hipMemcpy(d_idx.p, index, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        d_mean.alloc(std::max<uint64_t>(n, 1) * sizeof(double));
+        d_y.alloc(std::max<uint64_t>(n, 1) * sizeof(float));
+        d_out.alloc(std::max<uint64_t>(n, 1) * sizeof(double));
+        if (n) {
+            HIPCHK(hipMemcpy(d_mean.p, mean, n * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_y.p, y.data(), n * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(sbmf::fm_tgauss(seed, it, n, d_mean.as<double>(), d_y.as<float>(), d_idx.as<uint32_t>(), d_out.as<double>(),
+                                   nullptr));
+            HIPCHK(hipDeviceSynchronize());
+            HIPCHK(hipMemcpy(out, d_out.p, n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+    } else {
+        sbmf::fail(SBMF_E_ARG, "sbmf_test_tgauss: mode %d (0 device, 1 host)", mode);
+    }
     API_END(ctx)
 }
 

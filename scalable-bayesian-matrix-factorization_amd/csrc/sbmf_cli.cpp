@@ -202,6 +202,7 @@ struct RunState {
     bool vb = false;  // online VB prints "#Iter=..\tTest=.." (fm_learn_vb_online_simultaneous.h:447)
     bool lfm = false;  // libFM's fm_learn_mcmc chain: one attribute group with w (fm_learn_mcmc.h:1140-1149) ...
     uint32_t G = 1;    // ... or the -meta file's
+    bool cls = false;  // -task c: accuracies in place of RMSEs (fm_learn_mcmc_simultaneous.h:262-297)
     bool k1 = false;   // -dim k1: libFM logs wmu / wlambda (fm_learn_mcmc.h:422-431)
     bool avg_collected = false;  // the running mean divides by the collected sweeps
     uint32_t K = 0, ncol = 0;
@@ -221,14 +222,21 @@ struct RunState {
 // which libFM would log as vmu[g,f] / vlambda[g,f] of two attribute groups.
 // Our own columns follow at full precision, named sbmf_*.
 void rlog_header(std::ostream& o, const RunState& rs) {
-    o << "rmse\tmae\ttime_pred\ttime_learn\ttime_learn2\ttime_learn4\talpha\trmse_mcmc_this\trmse_mcmc_all";
-    if (!rs.vb) o << "\trmse_mcmc_all_but5";
+    if (rs.cls)  // fm_learn.h:118, fm_learn_mcmc.h:1129-1135
+        o << "accuracy\ttime_pred\ttime_learn\ttime_learn2\ttime_learn4\talpha\tacc_mcmc_this\tacc_mcmc_all"
+             "\tacc_mcmc_all_but5\tll_mcmc_this\tll_mcmc_all\tll_mcmc_all_but5";
+    else
+        o << "rmse\tmae\ttime_pred\ttime_learn\ttime_learn2\ttime_learn4\talpha\trmse_mcmc_this\trmse_mcmc_all";
+    if (!rs.vb && !rs.cls) o << "\trmse_mcmc_all_but5";
     const int ng = rs.lfm ? (int)rs.G : rs.vb ? 1 : 2;
     for (int g = 0; g < ng; ++g) {
         o << "\twmu[" << g << "]\twlambda[" << g << "]";
         for (uint32_t f = 0; f < rs.K; ++f) o << "\tvmu[" << g << "," << f << "]\tvlambda[" << g << "," << f << "]";
     }
-    o << "\tsbmf_iter\tsbmf_rmse_all\tsbmf_rmse_this\tsbmf_rmse_train\tsbmf_tau\tsbmf_ms_sweep\tsbmf_ms_eval\n";
+    if (rs.cls)
+        o << "\tsbmf_iter\tsbmf_acc_all\tsbmf_acc_this\tsbmf_acc_train\tsbmf_ll_this\tsbmf_tau\tsbmf_ms_sweep\tsbmf_ms_eval\n";
+    else
+        o << "\tsbmf_iter\tsbmf_rmse_all\tsbmf_rmse_this\tsbmf_rmse_train\tsbmf_tau\tsbmf_ms_sweep\tsbmf_ms_eval\n";
 }
 
 // rmse / mae of clamp(sum * norm) against the test targets (fm_learn_mcmc_simultaneous.h:307-324)
@@ -252,7 +260,7 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const uint64_t n = rs.test ? rs.test->n : 0;
     double mae = nan, rmse_but5 = nan;
-    if (n && !rs.vb) {
+    if (n && !rs.vb && !rs.cls) {
         // the running mean this sweep (clamped sums / divisor); its divisor gives the sums back
         rs.pred.resize(n);
         if (sbmf_predict(rs.ctx, rs.pred.data()) != SBMF_OK) throw std::runtime_error(sbmf_last_error(rs.ctx));
@@ -278,13 +286,21 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
     }
     const double tl = in->ms_sweep / 1000.0;
     // online VB logs time_learn* and rmse_mcmc_this only (fm_learn_vb_online_simultaneous.h:436-450)
-    o << (rs.vb ? nan : in->rmse_avg) << "\t" << mae << "\t" << nan << "\t" << tl << "\t" << tl << "\t" << tl << "\t";
+    if (rs.cls)
+        o << in->acc_avg << "\t" << nan << "\t" << tl << "\t" << tl << "\t" << tl << "\t";
+    else
+        o << (rs.vb ? nan : in->rmse_avg) << "\t" << mae << "\t" << nan << "\t" << tl << "\t" << tl << "\t" << tl << "\t";
     std::vector<double> h(4 * (size_t)rs.K, nan);
     double alpha = nan;
     if (!rs.vb && sbmf_get_hyper(rs.ctx, rs.lfm && rs.G > 1 ? nullptr : h.data(), &alpha) != SBMF_OK)
         throw std::runtime_error(sbmf_last_error(rs.ctx));
-    o << (rs.vb ? nan : alpha) << "\t" << in->rmse_this << "\t" << (rs.vb ? nan : in->rmse_avg);
-    if (!rs.vb) o << "\t" << rmse_but5;
+    if (rs.cls)  // acc_mcmc_all_but5, ll_mcmc_all and ll_mcmc_all_but5 are never computed by libFM (it logs
+                 // uninitialised variables, fm_learn_mcmc_simultaneous.h:263-286): nan here
+        o << alpha << "\t" << in->acc_this << "\t" << in->acc_avg << "\t" << nan << "\t" << in->ll_this << "\t" << nan
+          << "\t" << nan;
+    else
+        o << (rs.vb ? nan : alpha) << "\t" << in->rmse_this << "\t" << (rs.vb ? nan : in->rmse_avg);
+    if (!rs.vb && !rs.cls) o << "\t" << rmse_but5;
     const uint32_t K = rs.K;
     if (rs.vb) {
         o << "\t" << nan << "\t" << nan;
@@ -308,8 +324,12 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
         }
     }
     const std::streamsize pr = o.precision(17);
-    o << "\t" << in->sweep << "\t" << in->rmse_avg << "\t" << in->rmse_this << "\t" << in->rmse_train << "\t" << in->tau
-      << "\t" << in->ms_sweep << "\t" << in->ms_eval << "\n";
+    o << "\t" << in->sweep;
+    if (rs.cls)
+        o << "\t" << in->acc_avg << "\t" << in->acc_this << "\t" << in->acc_train << "\t" << in->ll_this;
+    else
+        o << "\t" << in->rmse_avg << "\t" << in->rmse_this << "\t" << in->rmse_train;
+    o << "\t" << in->tau << "\t" << in->ms_sweep << "\t" << in->ms_eval << "\n";
     o.precision(pr);
     o.flush();
 }
@@ -317,13 +337,16 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
 int on_sweep(const sbmf_sweep_info* in, void* user) {
     RunState* rs = static_cast<RunState*>(user);
     if (in->collected) rs->ncol++;
+    const double test = rs->cls ? in->acc_avg : in->rmse_avg;
     if (rs->vb)
         std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTest=" << in->rmse_avg << std::endl;
+    else if (rs->cls)  // fm_learn_mcmc_simultaneous.h:275 without its MAP@5 field
+        std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTrain=" << in->acc_train << "\tTest=" << test << std::endl;
     else
         std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTrain=" << in->rmse_train << "\tTest=" << in->rmse_avg
                   << std::endl;
     std::ofstream f(rs->rmse_file, std::ios_base::app);
-    f << in->rmse_avg << "\n";
+    if (!rs->cls) f << in->rmse_avg << "\n";  // libFM writes the file's lines in regression only (:245)
     if (rs->rlog) rlog_line(in, *rs);
     if (rs->verbosity > 0)
         std::cout << "  tau=" << in->tau << " sweep_ms=" << in->ms_sweep << " eval_ms=" << in->ms_eval << std::endl;
@@ -386,7 +409,8 @@ int main(int argc, char** argv) {
                   << "sbmf -- Scalable-BPMF Gibbs sampler for AMD Instinct MI355X (libFM command line)\n"
                   << "----------------------------------------------------------------------------" << std::endl;
         // libFM's flags (libfm.cpp:86-111)
-        cl.reg("task", "r=regression [MANDATORY]");
+        cl.reg("task", "r=regression, c=binary classification (libFM's probit model: targets <= 0 are the negative "
+                       "class; -method als and -method mcmc in libFM order only) [MANDATORY]");
         cl.reg("meta", "filename with one attribute group id per attribute (libFM's -meta): -method mcmc (libFM order) "
                        "and -method als draw their hyperparameters per group, and a two-feature input then takes the "
                        "general learner; ignored by the SBPMF sampler (-order sbpmf: one user and one item group) and "
@@ -455,9 +479,16 @@ int main(int argc, char** argv) {
         }
         cl.check();
         const std::string task = cl.get("task", "");
-        if (task != "r") throw std::runtime_error("only -task r (regression) is supported by the SBPMF sampler");
+        const char* task_refusal = "only -task r (regression) is supported by the SBPMF sampler";
+        if (task != "r" && task != "c") throw std::runtime_error(task_refusal);
+        const bool cls = task == "c";
         const std::string method = cl.get("method", "mcmc");
         const bool vb = method == "vb" || method == "vb_online";
+        // -task c is libFM's MCMC / ALS learner's: every other route is refused before a file is
+        // looked at where the flags alone decide it (-method vb, -order sbpmf, -quirks, triple input)
+        if (cls && (vb || cl.get("order", "") == "sbpmf" || (cl.has("quirks") && !cl.has("order")) ||
+                    cl.get("format", "auto") == "triple"))
+            throw std::runtime_error(task_refusal);
         const bool rec = cl.has("recommend");
         const char* rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
         if (rec && cl.get("recommend", "").empty()) throw std::runtime_error("-recommend needs a file name");
@@ -495,6 +526,7 @@ int main(int argc, char** argv) {
         const bool biased = q == "bias2" || q == "bias22";
         // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
         const bool lfm = als || (method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
+        if (cls && !lfm) throw std::runtime_error(task_refusal);
         if (rec && lfm) throw std::runtime_error(rec_refusal);
         if (recg && (lfm || biased)) throw std::runtime_error(recg_refusal);  // (a guest bias would need its own draw)
         if (method != "mcmc" && !vb && !als)
@@ -553,6 +585,7 @@ int main(int argc, char** argv) {
         cfg.split_chunk = (uint32_t)cl.getl("split_chunk", 0);
         cfg.eval_train = vb ? 0 : 1;
         cfg.method = vb ? SBMF_METHOD_VB : als ? SBMF_METHOD_ALS : lfm ? SBMF_METHOD_LIBFM_MCMC : SBMF_METHOD_MCMC;
+        cfg.task = cls ? SBMF_TASK_CLASSIFICATION : SBMF_TASK_REGRESSION;
         if (lfm) {
             cfg.libfm_dim = (dim[0] ? 1u : 0u) | (dim[1] ? 2u : 0u);
             if (!cl.has("init_stdev")) cfg.init_stdev = 0.1;  // libfm.cpp:127
@@ -730,6 +763,7 @@ int main(int argc, char** argv) {
         rs.rmse_file = "test_rmse_" + nm.str() + "_" + (vb ? std::string("vb_online") : std::string("mcmc"));
         rs.vb = vb;
         rs.lfm = lfm;
+        rs.cls = cls;
         rs.G = grouped ? nmeta_groups : 1;
         rs.k1 = dim[1] != 0;
         rs.K = cfg.num_factor;

@@ -886,6 +886,7 @@ struct SweepRun {
             // for this sweep's results (ev[9]) and runs the callback
             if (!overlap) HIPCHK(hipEventSynchronize(c->ev[9]));
             sbmf_sweep_info info{};
+            info.acc_train = info.acc_avg = info.acc_this = info.ll_this = NAN;  // regression
             info.sweep = c->sweep;
             info.collected = collect ? 1u : 0u;
             info.tau = hy.tau;

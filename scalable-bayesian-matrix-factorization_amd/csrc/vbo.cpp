@@ -794,6 +794,7 @@ void VBLearner::run(uint32_t epochs, sbmf_sweep_cb cb, void* user) {
         info.rmse_avg = rmse;
         info.rmse_this = rmse;
         info.rmse_train = NAN;
+        info.acc_train = info.acc_avg = info.acc_this = info.ll_this = NAN;  // regression
         info.tau = sc.alpha;
         info.ms_sweep = ms_epoch;
         info.ms_eval = ms_eval;

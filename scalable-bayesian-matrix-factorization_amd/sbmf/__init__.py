@@ -299,14 +299,21 @@ class FMLearnSBPMF:
     def __init__(self, num_factor=20, num_iter=100, seed=1, rng="ref", quirks="final", precision="f64", burnin=0,
                  device=0, init_stdev=None, recompute_every=1, eval_train=False,
                  stream_threshold=0, split_chunk=0, tune=0, method="mcmc", vb_batches=0, average="default",
-                 order="sbpmf", k0=1, k1=1, regular=(0.0, 0.0, 0.0), **hyper):
+                 order="sbpmf", k0=1, k1=1, regular=(0.0, 0.0, 0.0), task="r", **hyper):
         """method "mcmc" with order "sbpmf" (default): the SBPMF Gibbs sampler;
         method "mcmc" with order "libfm": libFM's own MCMC chain (f-outer, one
         hyperprior group, w0 / w with k0 / k1, -regular = ``regular``);
         "als": libFM's ALS (the same learner without sampling); "vb": online VB.
         With attribute groups (``set_groups``) ``regular`` may hold 1 + 2G values
-        (r0, w_lambda per group, v_lambda per group), as libFM's -regular with -meta."""
+        (r0, w_lambda per group, v_lambda per group), as libFM's -regular with -meta.
+        task "c" (libFM's -task c; order "libfm" or method "als" only): binary classification with a
+        probit model -- targets <= 0 are the negative class, ``history`` carries ``acc_train``,
+        ``acc_avg``, ``acc_this`` and ``ll_this`` (the ``rmse_*`` are NaN), ``acc_trajectory`` is the
+        running-mean test accuracy and ``predict()`` returns probabilities in [0, 1]."""
         self.cfg = config_default()
+        if task not in ("r", "c"):
+            raise ValueError("task must be r (regression) or c (classification)")
+        self.cfg.task = _lib.TASK_CLASSIFICATION if task == "c" else _lib.TASK_REGRESSION
         if method not in ("mcmc", "vb", "vb_online", "als") or order not in ("sbpmf", "libfm"):
             raise ValueError("method must be mcmc, als or vb (order sbpmf or libfm)")
         if method in ("vb", "vb_online"):
@@ -443,7 +450,13 @@ class FMLearnSBPMF:
     def rmse_trajectory(self):
         return np.array([h["rmse_avg"] for h in self.history])
 
-    # -- fm_learn::predict (fm_learn.h:191): averaged clamped predictions of the test set
+    @property
+    def acc_trajectory(self):
+        """task "c": the per-sweep test accuracy of the running-mean probability (libFM's "Test=")."""
+        return np.array([h["acc_avg"] for h in self.history])
+
+    # -- fm_learn::predict (fm_learn.h:191): averaged clamped predictions of the test set (task "c":
+    # the probabilities of the positive class, clipped to [0, 1])
     def predict(self):
         out = np.zeros(self._test.num_cases if self._test is not None else 0)
         self._check(lib.sbmf_predict(self.ctx, _ptr(out, C.c_double)))
@@ -634,6 +647,24 @@ def device_usage(device=0):
     if rc != SBMF_OK:
         raise SBMFError(rc, lib.sbmf_last_global_error().decode())
     return {f: getattr(u, f) for f, _ in u._fields_}
+
+
+def tgauss(mean, sign, seed=1, it=0, mode="device", index=None, device=0):
+    """sbmf_test_tgauss: the latent targets of classification for cases with the predictions
+    ``mean`` and labels ``sign`` (>= 0: the positive class) -- mode "device": the Philox draw of
+    the train frames at the key (seed, it, index[i] or i); mode "host": the reference's truncated
+    normals over its own stream seeded with ``seed``, drawn in order (no GPU needed)."""
+    mean = _f64(mean).ravel()
+    sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sign, np.int32), mean.shape))
+    idx = None if index is None else _u32(index).ravel()
+    out = np.zeros(len(mean))
+    rc = lib.sbmf_test_tgauss(0 if mode == "device" else 1, device, seed, it, len(mean), _ptr(mean, C.c_double),
+                              _ptr(sg, C.c_int32), None if idx is None else _ptr(idx, C.c_uint32),
+                              _ptr(out, C.c_double))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    return out
+
 
 
 class Communicator:

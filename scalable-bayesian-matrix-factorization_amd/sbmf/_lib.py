@@ -16,6 +16,7 @@ RNG_REFERENCE, RNG_PHILOX = 0, 1
 QUIRKS_FINAL, QUIRKS_SBPMF2, QUIRKS_NONE, QUIRKS_BIAS2, QUIRKS_BIAS22 = 0, 1, 2, 3, 4
 F64, F32 = 0, 1
 METHOD_MCMC, METHOD_VB, METHOD_LIBFM_MCMC, METHOD_ALS = 0, 1, 2, 3
+TASK_REGRESSION, TASK_CLASSIFICATION = 0, 1
 NKIND = 11  # SBMF_NKIND
 KIND_NAMES = ['gblock_w4', 'gblock_w16', 'gblock_b2', 'gblock_b4', 'gblock_b8', 'gres_stage', 'rows_w2', 'rows_w8',
               'rows_b4', 'rows_b8', 'gram']
@@ -32,7 +33,7 @@ class Config(C.Structure):
         ("gram_threshold", C.c_uint32), ("row_kernel", C.c_uint32), ("stream_threshold", C.c_uint32),
         ("split_chunk", C.c_uint32), ("tune", C.c_uint32), ("method", C.c_uint32), ("vb_batches", C.c_uint32),
         ("average", C.c_uint32), ("libfm_dim", C.c_uint32), ("reg0", C.c_double), ("regw", C.c_double),
-        ("regv", C.c_double), ("pipeline", C.c_uint32),
+        ("regv", C.c_double), ("pipeline", C.c_uint32), ("task", C.c_uint32),
     ]
 
 
@@ -40,6 +41,7 @@ class SweepInfo(C.Structure):
     _fields_ = [
         ("sweep", C.c_uint32), ("collected", C.c_uint32), ("rmse_avg", C.c_double), ("rmse_this", C.c_double),
         ("rmse_train", C.c_double), ("tau", C.c_double), ("ms_sweep", C.c_double), ("ms_eval", C.c_double),
+        ("acc_train", C.c_double), ("acc_avg", C.c_double), ("acc_this", C.c_double), ("ll_this", C.c_double),
     ]
 
 
@@ -144,6 +146,8 @@ SIGNATURES = {
     "sbmf_get_fm_groups": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_F64, _P_F64, _P_F64, _P_F64]),
     "sbmf_load_libfm_meta": (C.c_int, [C.c_char_p, C.c_uint32, _P_U32, _P_U32]),
     "sbmf_test_fm_group_sums": (C.c_int, [C.c_void_p, _P_F64]),
+    "sbmf_test_tgauss": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, _P_F64,
+                                   C.POINTER(C.c_int32), _P_U32, _P_F64]),
     "sbmf_partition_rows": (C.c_int, [_P_U32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "sbmf_ref_stream": (C.c_int, [C.c_uint32, C.c_int, C.c_double, C.c_uint64, _P_F64]),
     "sbmf_philox_normals": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P_F64]),
