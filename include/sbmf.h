@@ -597,6 +597,60 @@ int sbmf_get_fm_groups(sbmf_ctx* ctx, uint32_t* G, uint32_t* cnt, double* w_lamb
  * after the first num_attr are ignored.  Host only. */
 int sbmf_load_libfm_meta(const char* path, uint32_t num_attr, uint32_t* group, uint32_t* G);
 
+/* --- libFM's block-structure relations (bin/libFM -relation) ------------------------------- */
+/* A relation holds features that are a property of one field of the cases -- the user's
+ * age and occupation, the item's genres -- once per value of that field (a "block row")
+ * instead of once per case (relation.h; fm_learn_mcmc.h relation_cache :57-65, draw_all
+ * :458-491 and :521-620, draw_w_rel :721-777, draw_v_rel :839-899, the block rows' part
+ * of predict_data_and_write_to_eterms :117-348).  The chain is the one of the same cases
+ * with the block rows' features written out on every case; the relation's attributes are
+ * drawn from per-block-row sums, so their passes touch block->n rows, not the cases.
+ *
+ * block: the block table as cases (targets ignored, target may be NULL); block->num_attr is
+ * the relation's num_feature.  train_row[c] / test_row[c]: the block row case c of the train /
+ * test set joins.  group[a] for a < block->num_attr with G = the number of the relation's own
+ * groups (its .groups file), or NULL / 0 for one group.  Every array is copied.
+ *
+ * Call after the train / test data is set (sbmf_set_train_cases, or sbmf_set_train: triples
+ * given a relation run through the general learner, as triples given groups do) and before
+ * sbmf_prepare, once per relation in -relation order; at most 4 relations.
+ *
+ * Attribute ids (libfm.cpp:328-341): relation 0's attributes follow the main table's
+ * num_attribute = max(train, test num_attr) + 1, relation r + 1's follow relation r's
+ * block->num_attr ids (no + 1 there); num_attribute of the model is the final sum, and
+ * sbmf_get_fm / sbmf_fm_info speak of that joined space.  Groups (:343-364): the main
+ * table's (1, or those of sbmf_set_attr_groups, which keeps describing the main ids only),
+ * then each relation's; sbmf_set_group_regular -- called after the last sbmf_add_relation --
+ * and sbmf_get_fm_groups speak of the joined groups.
+ *
+ * SBMF_E_ARG, each naming the numbers: a row index >= block->n, a map whose length is not
+ * the set's case count, an attribute repeated inside a block row, an attribute >=
+ * block->num_attr, a group >= G, a fifth relation.  SBMF_E_STATE: another method (named), a
+ * context that joined a communicator or is a virtual rank (named), no data yet, data
+ * already prepared. */
+int sbmf_add_relation(sbmf_ctx* ctx, const sbmf_cases* block, const uint32_t* train_row, uint64_t n_train,
+                      const uint32_t* test_row, uint64_t n_test, const uint32_t* group, uint32_t G);
+/* After sbmf_prepare: *nrel relations, and for the first min(*nrel, cap) of them the first
+ * attribute id, the attribute count, the block rows, the ranges of the block table
+ * (sbmf_fm_ranges applied to it: the relation's launches per row-length bin), the first
+ * group id and the group count.  Any pointer may be NULL. */
+int sbmf_fm_relation_info(sbmf_ctx* ctx, uint32_t* nrel, uint32_t cap, uint32_t* attr_offset, uint32_t* num_attr,
+                          uint32_t* block_rows, uint32_t* nranges, uint32_t* group_offset, uint32_t* num_groups);
+/* libFM's relation files (relation.h): <stem>.xt or, failing that, <stem>.x -- the block table
+ * as libFM's binary sparse matrix (fmatrix.h; rows = block rows in .x, attributes in .xt) --
+ * into block (targets 0; num_attr = the file's num_feature); <stem>.train / <stem>.test, the
+ * block row of every case, as text (one unsigned integer per case) or as a binary
+ * DVector<uint> (RelationJoin::load, relation.h:65-88); and the optional <stem>.groups into
+ * *group ([block->num_attr], *G = the largest + 1; NULL and 0 without the file).  IO errors
+ * (sbmf_loader_error) name the file and the entry.  Free with sbmf_free_relation.  Host only. */
+int sbmf_load_libfm_relation(const char* stem, sbmf_cases* block, uint32_t** train_row, uint64_t* n_train,
+                             uint32_t** test_row, uint64_t* n_test, uint32_t** group, uint32_t* G);
+void sbmf_free_relation(sbmf_cases* block, uint32_t** train_row, uint32_t** test_row, uint32_t** group);
+/* The writers of those files: a block table as <path> in the .x layout (rows = block rows), and
+ * a map as text (binary = 0) or as a binary DVector<uint>.  Host only. */
+int sbmf_save_libfm_block(const char* path, const sbmf_cases* block);
+int sbmf_save_libfm_row_map(const char* path, const uint32_t* row, uint64_t n, int binary);
+
 /* --- multi-GPU layout (host only) ---------------------------------------------------------- */
 /* The row partition every rank uses: contiguous row blocks balanced by
  * ratings (ptr = CSR/CSC offsets [R+1]), boundaries rounded to 256 rows.

@@ -261,6 +261,7 @@ struct sbmf_ctx {
     // as cases; the model then still reads back by user / item)
     FMChain* fm = nullptr;
     FMGroups fmgroups;  // sbmf_set_attr_groups / sbmf_set_group_regular, read at sbmf_prepare
+    std::vector<FMRelation> fmrels;  // sbmf_add_relation, in the order given, read at sbmf_prepare
     struct HostCases {
         std::vector<uint64_t> ptr;
         std::vector<uint32_t> attr;

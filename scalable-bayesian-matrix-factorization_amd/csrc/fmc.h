@@ -57,6 +57,12 @@ struct FMChain {
     uint32_t it = 0, n_launch = 0;
     uint32_t nranges = 0;   // the general learner's ranges (the two-attribute learner has none: 0)
     uint32_t I = 0, J = 0;  // users-first layout (user u -> attribute u, item i -> I + i); I = 0: cases, no such view
+    // the general learner's relations (libFM's -relation), in the order given: where a relation's
+    // attributes and groups sit in the joined spaces, its block rows and the ranges of its table
+    struct RelInfo {
+        uint32_t attr_offset, num_attr, block_rows, nranges, group_offset, G;
+    };
+    std::vector<RelInfo> rel_info;
     GlibcRand grand{1};
     hipStream_t st = nullptr;
     hipEvent_t ev[3] = {};

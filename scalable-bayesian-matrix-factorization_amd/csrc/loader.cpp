@@ -1239,3 +1239,220 @@ int sbmf_load_libfm_cases(const char* path, sbmf_cases* out) {
 }
 
 }  // extern "C"
+
+// ---- libFM's block-structure relations (relation.h): <stem>.xt or <stem>.x (the block table as a
+// binary sparse matrix, the layout above), <stem>.train / <stem>.test (the block row of every case:
+// text, one unsigned integer per case, or a binary DVector<uint>: u32 version = 1; u32 size = 4;
+// u32 dim; dim x u32 -- RelationJoin::load, relation.h:65-88) and the optional <stem>.groups.
+namespace {
+
+// a binary sparse matrix as rows of {id, value}: ptr[num_rows + 1], ids, values
+int read_fmatrix(const std::string& path, FmHeader& h, std::vector<uint64_t>& ptr, std::vector<uint32_t>& id,
+                 std::vector<float>& val) {
+    InFile in;
+    if (!open_in(path.c_str(), in)) {
+        g_lerr = "unable to open " + path;
+        return SBMF_E_IO;
+    }
+    if (in.n < sizeof h) {
+        g_lerr = path + ": truncated header";
+        return SBMF_E_IO;
+    }
+    std::memcpy(&h, in.p, sizeof h);
+    if (h.id != 2 || h.float_size != sizeof(float)) {
+        g_lerr = path + ": not a libFM sparse matrix file (id 2, 4-byte values)";
+        return SBMF_E_IO;
+    }
+    ptr.assign((size_t)h.num_rows + 1, 0);
+    id.clear();
+    val.clear();
+    size_t at = sizeof h;
+    for (uint32_t r = 0; r < h.num_rows; ++r) {
+        uint32_t sz = 0;
+        if (at + 4 > in.n || (std::memcpy(&sz, in.p + at, 4), at + 4 + (size_t)sz * 8 > in.n)) {
+            g_lerr = path + ": truncated at row " + std::to_string(r);
+            return SBMF_E_IO;
+        }
+        at += 4;
+        for (uint32_t k = 0; k < sz; ++k, at += 8) {
+            uint32_t a;
+            float v;
+            std::memcpy(&a, in.p + at, 4);
+            std::memcpy(&v, in.p + at + 4, 4);
+            if (a >= h.num_cols) {
+                g_lerr = path + " row " + std::to_string(r) + ": entry " + std::to_string(k) + " has id " +
+                         std::to_string(a) + "; the file has " + std::to_string(h.num_cols) + " columns";
+                return SBMF_E_IO;
+            }
+            id.push_back(a);
+            val.push_back(v);
+        }
+        ptr[r + 1] = id.size();
+    }
+    if (id.size() != h.num_values) {
+        g_lerr = path + ": " + std::to_string(id.size()) + " entries read, the header says " + std::to_string(h.num_values);
+        return SBMF_E_IO;
+    }
+    return SBMF_OK;
+}
+
+// the block row of every case, in either form
+int read_row_map(const std::string& path, uint32_t** out, uint64_t* n) {
+    *out = nullptr;
+    *n = 0;
+    InFile in;
+    if (!open_in(path.c_str(), in)) {
+        g_lerr = "unable to open " + path;
+        return SBMF_E_IO;
+    }
+    std::vector<uint32_t> v;
+    uint32_t hd[3] = {0, 0, 0};
+    if (in.n >= 8) std::memcpy(hd, in.p, in.n >= 12 ? 12 : 8);
+    if (in.n >= 8 && hd[0] == 1 && hd[1] == sizeof(uint32_t)) {  // RelationJoin::load's test for the binary form
+        if (in.n < 12 || in.n < 12 + (size_t)hd[2] * 4) {
+            g_lerr = path + ": a binary DVector<uint> of " + std::to_string(hd[2]) + " entries, truncated";
+            return SBMF_E_IO;
+        }
+        v.resize(hd[2]);
+        if (hd[2]) std::memcpy(v.data(), in.p + 12, (size_t)hd[2] * 4);
+    } else {
+        const char *q = in.p, *end = in.p + in.n;
+        auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; };
+        for (;;) {
+            while (q < end && space(*q)) ++q;
+            if (q == end) break;
+            uint64_t x = 0;
+            const char* b = q;
+            while (q < end && *q >= '0' && *q <= '9' && x <= 0xffffffffull) x = x * 10 + (uint64_t)(*q++ - '0');
+            if (q == b || (q < end && !space(*q)) || x > 0xfffffffeull) {
+                g_lerr = path + ": entry " + std::to_string(v.size() + 1) + " is not a block-row index (an unsigned integer)";
+                return SBMF_E_IO;
+            }
+            v.push_back((uint32_t)x);
+        }
+    }
+    *out = static_cast<uint32_t*>(std::malloc(std::max<size_t>(v.size(), 1) * sizeof(uint32_t)));
+    if (!*out) return SBMF_E_NOMEM;
+    std::copy(v.begin(), v.end(), *out);
+    *n = v.size();
+    return SBMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sbmf_free_relation(sbmf_cases* block, uint32_t** train_row, uint32_t** test_row, uint32_t** group) {
+    sbmf_free_cases(block);
+    for (uint32_t** p : {train_row, test_row, group})
+        if (p) {
+            std::free(*p);
+            *p = nullptr;
+        }
+}
+
+int sbmf_load_libfm_relation(const char* stem, sbmf_cases* block, uint32_t** train_row, uint64_t* n_train,
+                             uint32_t** test_row, uint64_t* n_test, uint32_t** group, uint32_t* G) {
+    if (!stem || !block || !train_row || !n_train || !test_row || !n_test || !group || !G) return SBMF_E_ARG;
+    std::memset(block, 0, sizeof *block);
+    *train_row = *test_row = *group = nullptr;
+    *n_train = *n_test = 0;
+    *G = 0;
+    const std::string s(stem);
+    FmHeader h{};
+    std::vector<uint64_t> ptr;
+    std::vector<uint32_t> id;
+    std::vector<float> val;
+    const bool t = file_exists(s + ".xt");
+    if (!t && !file_exists(s + ".x")) {
+        g_lerr = "unable to open " + s + ".xt (or .x)";
+        return SBMF_E_IO;
+    }
+    int rc = read_fmatrix(s + (t ? ".xt" : ".x"), h, ptr, id, val);
+    if (rc != SBMF_OK) return rc;
+    // .xt: a row is an attribute and its entries the block rows holding it, ascending
+    const uint32_t nb = t ? h.num_cols : h.num_rows, pa = t ? h.num_rows : h.num_cols;
+    const size_t nnz = id.size();
+    block->n = nb;
+    block->nnz = nnz;
+    block->num_attr = pa;
+    block->ptr = static_cast<uint64_t*>(std::calloc((size_t)nb + 1, sizeof(uint64_t)));
+    block->attr = static_cast<uint32_t*>(std::malloc(std::max<size_t>(nnz, 1) * sizeof(uint32_t)));
+    block->x = static_cast<float*>(std::malloc(std::max<size_t>(nnz, 1) * sizeof(float)));
+    block->target = static_cast<float*>(std::calloc(std::max<size_t>(nb, 1), sizeof(float)));
+    auto bail = [&](int code) {
+        sbmf_free_relation(block, train_row, test_row, group);
+        return code;
+    };
+    if (!block->ptr || !block->attr || !block->x || !block->target) return bail(SBMF_E_NOMEM);
+    if (t) {
+        for (size_t k = 0; k < nnz; ++k) block->ptr[id[k] + 1]++;
+        for (uint32_t j = 0; j < nb; ++j) block->ptr[j + 1] += block->ptr[j];
+        std::vector<uint64_t> fill(block->ptr, block->ptr + nb);
+        for (uint32_t a = 0; a < pa; ++a)
+            for (uint64_t k = ptr[a]; k < ptr[a + 1]; ++k) {
+                const uint64_t at = fill[id[k]]++;
+                block->attr[at] = a;
+                block->x[at] = val[k];
+            }
+    } else {
+        std::copy(ptr.begin(), ptr.end(), block->ptr);
+        std::copy(id.begin(), id.end(), block->attr);
+        std::copy(val.begin(), val.end(), block->x);
+    }
+    if ((rc = read_row_map(s + ".train", train_row, n_train)) != SBMF_OK) return bail(rc);
+    if ((rc = read_row_map(s + ".test", test_row, n_test)) != SBMF_OK) return bail(rc);
+    if (file_exists(s + ".groups")) {
+        *group = static_cast<uint32_t*>(std::malloc(std::max<size_t>(pa, 1) * sizeof(uint32_t)));
+        if (!*group) return bail(SBMF_E_NOMEM);
+        if ((rc = sbmf_load_libfm_meta((s + ".groups").c_str(), pa, *group, G)) != SBMF_OK) return bail(rc);
+    }
+    return SBMF_OK;
+}
+
+int sbmf_save_libfm_block(const char* path, const sbmf_cases* block) {
+    if (!path || !block || (block->n && !block->ptr) || (block->nnz && (!block->attr || !block->x))) return SBMF_E_ARG;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) {
+        g_lerr = std::string("unable to open ") + path + " for writing";
+        return SBMF_E_IO;
+    }
+    FmHeader h{2, (uint32_t)sizeof(float), block->nnz, (uint32_t)block->n, block->num_attr};
+    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
+    for (uint64_t j = 0; j < block->n && ok; ++j) {
+        const uint32_t sz = (uint32_t)(block->ptr[j + 1] - block->ptr[j]);
+        ok = std::fwrite(&sz, 4, 1, f) == 1;
+        for (uint64_t k = block->ptr[j]; k < block->ptr[j + 1] && ok; ++k)
+            ok = std::fwrite(&block->attr[k], 4, 1, f) == 1 && std::fwrite(&block->x[k], 4, 1, f) == 1;
+    }
+    ok = (std::fclose(f) == 0) & ok;
+    if (!ok) {
+        g_lerr = std::string("write error on ") + path;
+        return SBMF_E_IO;
+    }
+    return SBMF_OK;
+}
+
+int sbmf_save_libfm_row_map(const char* path, const uint32_t* row, uint64_t n, int binary) {
+    if (!path || (n && !row) || n > 0xffffffffull) return SBMF_E_ARG;
+    FILE* f = std::fopen(path, binary ? "wb" : "w");
+    if (!f) {
+        g_lerr = std::string("unable to open ") + path + " for writing";
+        return SBMF_E_IO;
+    }
+    bool ok = true;
+    if (binary) {
+        const uint32_t hd[3] = {1, (uint32_t)sizeof(uint32_t), (uint32_t)n};
+        ok = std::fwrite(hd, sizeof hd, 1, f) == 1 && (n == 0 || std::fwrite(row, 4, n, f) == n);
+    } else {
+        for (uint64_t c = 0; c < n && ok; ++c) ok = std::fprintf(f, "%u\n", row[c]) > 0;
+    }
+    ok = (std::fclose(f) == 0) & ok;
+    if (!ok) {
+        g_lerr = std::string("write error on ") + path;
+        return SBMF_E_IO;
+    }
+    return SBMF_OK;
+}
+
+}  // extern "C"

@@ -325,7 +325,7 @@ static void prepare_cases(sbmf_ctx* c, bool triples) {
         sbmf::fail(SBMF_E_STATE, "the general libFM learner (cases with any number of features) runs on one rank: "
                                  "this context joined a communicator or is a virtual rank");
     c->K = c->cfg.num_factor;
-    c->fm = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st, &c->fmgroups);
+    c->fm = fmg_create(c->cfg, c->ctr.view(), c->cte.view(), c->st, &c->fmgroups, &c->fmrels);
     if (triples) {  // the users-first layout: the model reads back by user / item
         c->fm->I = c->I;
         c->fm->J = c->J;
@@ -382,7 +382,7 @@ static void prepare_ctx(sbmf_ctx* c) {
     // a triples context given attribute groups takes the general learner: the two-attribute
     // kernels (fmm.hip) keep one group
     const char* gen = std::getenv("SBMF_FMM_GENERAL");
-    const bool grouped = !c->fmgroups.group.empty() || !c->fmgroups.regw.empty();
+    const bool grouped = !c->fmgroups.group.empty() || !c->fmgroups.regw.empty() || !c->fmrels.empty();
     if (libfm_method(c) && ((gen && std::atoi(gen) != 0) || grouped)) {
         triples_to_cases(c->tu, c->ti, c->tr, c->I, c->ctr);
         triples_to_cases(c->su, c->si, c->sr, c->I, c->cte);
@@ -552,13 +552,120 @@ int sbmf_set_group_regular(sbmf_ctx* ctx, uint32_t G, const double* regw, const 
     API_BEGIN
     check_groups_ctx(ctx, "sbmf_set_group_regular");
     if (G && (!regw || !regv)) sbmf::fail(SBMF_E_ARG, "sbmf_set_group_regular: null array with G > 0");
-    if (!ctx->fmgroups.group.empty()) {
-        const uint32_t have = *std::max_element(ctx->fmgroups.group.begin(), ctx->fmgroups.group.end()) + 1;
-        if (G && G != have)
+    if (!ctx->fmgroups.group.empty() || !ctx->fmrels.empty()) {
+        // the joined groups: the main table's, then every relation's own
+        uint32_t have = ctx->fmgroups.group.empty()
+                            ? 1 : *std::max_element(ctx->fmgroups.group.begin(), ctx->fmgroups.group.end()) + 1;
+        for (const sbmf::FMRelation& r : ctx->fmrels) have += r.G;
+        if (G && G != have && ctx->fmrels.empty())
             sbmf::fail(SBMF_E_ARG, "sbmf_set_group_regular: %u groups given, sbmf_set_attr_groups set %u", G, have);
+        else if (G && G != have)
+            sbmf::fail(SBMF_E_ARG, "sbmf_set_group_regular: %u groups given, sbmf_set_attr_groups and the %zu "
+                                   "relations set %u", G, ctx->fmrels.size(), have);
     }
     ctx->fmgroups.regw.assign(regw, regw + G);
     ctx->fmgroups.regv.assign(regv, regv + G);
+    API_END(ctx)
+}
+
+// ---- libFM's block-structure relations (-relation)
+int sbmf_add_relation(sbmf_ctx* ctx, const sbmf_cases* block, const uint32_t* train_row, uint64_t n_train,
+                      const uint32_t* test_row, uint64_t n_test, const uint32_t* group, uint32_t G) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (ctx->prepared) sbmf::fail(SBMF_E_STATE, "sbmf_add_relation: data already prepared");
+    static const char* const names[] = {"mcmc (the SBPMF sampler)", "vb (online VB)", "mcmc, libFM order", "als"};
+    if (ctx->virt)
+        sbmf::fail(SBMF_E_STATE, "sbmf_add_relation: this context is a virtual rank; relations run on one rank");
+    if (ctx->nranks > 1 || ctx->comm != &ctx->own_comm || ctx->own_comm.active())
+        sbmf::fail(SBMF_E_STATE, "sbmf_add_relation: this context joined a communicator; relations run on one rank");
+    if (!libfm_method(ctx))
+        sbmf::fail(SBMF_E_STATE, "sbmf_add_relation: relations belong to libFM's MCMC / ALS learner "
+                                 "(SBMF_METHOD_LIBFM_MCMC, SBMF_METHOD_ALS); this context runs method %s",
+                   names[ctx->cfg.method]);
+    if (!ctx->ctr.set && ctx->tu.empty())
+        sbmf::fail(SBMF_E_STATE, "sbmf_add_relation: give the train / test cases first (the maps are checked against them)");
+    if (ctx->fmrels.size() >= sbmf::FG_MAX_REL)
+        sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: a context takes at most %u relations", sbmf::FG_MAX_REL);
+    if (!block) sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: null block table");
+    if ((block->n && !block->ptr) || (block->nnz && (!block->attr || !block->x)) || (n_train && !train_row) ||
+        (n_test && !test_row))
+        sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: null array");
+    if (block->n && (block->ptr[0] != 0 || block->ptr[block->n] != block->nnz))
+        sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: ptr must run from 0 to nnz");
+    const uint64_t have_tr = ctx->ctr.set ? ctx->ctr.y.size() : ctx->tu.size();
+    const uint64_t have_te = ctx->ctr.set ? ctx->cte.y.size() : ctx->su.size();
+    if (n_train != have_tr)
+        sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: the train map holds %llu block-row indices, the train set %llu cases",
+                   (unsigned long long)n_train, (unsigned long long)have_tr);
+    if (n_test != have_te)
+        sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: the test map holds %llu block-row indices, the test set %llu cases",
+                   (unsigned long long)n_test, (unsigned long long)have_te);
+    for (uint64_t q = 0; q < n_train; ++q)
+        if (train_row[q] >= block->n)
+            sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: train case %llu joins block row %u; the block table has %llu rows",
+                       (unsigned long long)q, train_row[q], (unsigned long long)block->n);
+    for (uint64_t q = 0; q < n_test; ++q)
+        if (test_row[q] >= block->n)
+            sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: test case %llu joins block row %u; the block table has %llu rows",
+                       (unsigned long long)q, test_row[q], (unsigned long long)block->n);
+    sbmf::FMRelation r;
+    r.ptr.assign(block->n + 1, 0);
+    if (block->n) r.ptr.assign(block->ptr, block->ptr + block->n + 1);
+    r.attr.assign(block->attr, block->attr + block->nnz);
+    r.x.assign(block->x, block->x + block->nnz);
+    r.num_attr = block->num_attr;
+    std::vector<std::pair<uint32_t, float>> tmp;
+    for (uint64_t j = 0; j < block->n; ++j) {  // entries by attribute within a block row, as set_cases
+        const uint64_t b = r.ptr[j], e = r.ptr[j + 1];
+        if (e < b || e > block->nnz)
+            sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: ptr decreases at block row %llu", (unsigned long long)j);
+        tmp.clear();
+        for (uint64_t k = b; k < e; ++k) {
+            if (r.attr[k] >= block->num_attr)
+                sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: block row %llu holds attribute %u >= num_attr %u",
+                           (unsigned long long)j, r.attr[k], block->num_attr);
+            tmp.emplace_back(r.attr[k], r.x[k]);
+        }
+        std::stable_sort(tmp.begin(), tmp.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
+        for (uint64_t k = b; k < e; ++k) {
+            r.attr[k] = tmp[k - b].first;
+            r.x[k] = tmp[k - b].second;
+            if (k > b && r.attr[k - 1] == r.attr[k])
+                sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: block row %llu repeats attribute %u (the passes write one "
+                                       "record per block row of an attribute)", (unsigned long long)j, r.attr[k]);
+        }
+    }
+    r.train_row.assign(train_row, train_row + n_train);
+    r.test_row.assign(test_row, test_row + n_test);
+    if (group && G) {
+        r.group.assign(group, group + block->num_attr);
+        for (uint32_t a = 0; a < block->num_attr; ++a)
+            if (group[a] >= G)
+                sbmf::fail(SBMF_E_ARG, "sbmf_add_relation: attribute %u has group %u; G = %u", a, group[a], G);
+        r.G = G;
+    }
+    ctx->fmrels.push_back(std::move(r));
+    API_END(ctx)
+}
+
+int sbmf_fm_relation_info(sbmf_ctx* ctx, uint32_t* nrel, uint32_t cap, uint32_t* attr_offset, uint32_t* num_attr,
+                          uint32_t* block_rows, uint32_t* nranges, uint32_t* group_offset, uint32_t* num_groups) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (!ctx->prepared) sbmf::fail(SBMF_E_STATE, "not prepared");
+    if (!ctx->fm || !ctx->fm->nranges)
+        sbmf::fail(SBMF_E_STATE, "sbmf_fm_relation_info: this context does not run the general libFM learner");
+    const auto& ri = ctx->fm->rel_info;
+    if (nrel) *nrel = (uint32_t)ri.size();
+    for (uint32_t r = 0; r < ri.size() && r < cap; ++r) {
+        if (attr_offset) attr_offset[r] = ri[r].attr_offset;
+        if (num_attr) num_attr[r] = ri[r].num_attr;
+        if (block_rows) block_rows[r] = ri[r].block_rows;
+        if (nranges) nranges[r] = ri[r].nranges;
+        if (group_offset) group_offset[r] = ri[r].group_offset;
+        if (num_groups) num_groups[r] = ri[r].G;
+    }
     API_END(ctx)
 }
 

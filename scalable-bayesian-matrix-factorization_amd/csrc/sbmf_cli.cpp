@@ -437,7 +437,8 @@ int main(int argc, char** argv) {
         cl.reg("rlog", "write per-sweep measurements to a TSV file; default=''");
         cl.reg("seed", "integer seed; default=1 (glibc default seed of the reference samplers)");
         cl.reg("help", "this screen");
-        cl.reg("relation", "unused (block structure relations)");
+        cl.reg("relation", "BS: comma-separated stems of block-structure relations (libFM's -relation: <stem>.xt or .x, "
+                           "<stem>.train, <stem>.test, optional <stem>.groups): -method mcmc (libFM order) and -method als");
         cl.reg("cache_size", "unused (binary data format)");
         // sampler settings
         cl.reg("rng", "ref (reference glibc/Leva/Marsaglia-Tsang stream; default) | philox (in-kernel, throughput)");
@@ -527,6 +528,12 @@ int main(int argc, char** argv) {
         // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
         const bool lfm = als || (method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
         if (cls && !lfm) throw std::runtime_error(task_refusal);
+        // unlike -meta, -relation cannot be ignored: the relations' features would be missing (before any file is opened)
+        if (!lfm && !cl.get("relation", "").empty())
+            throw std::runtime_error(std::string("-relation: block-structure relations are drawn by libFM's MCMC / ALS learner "
+                                                 "(-method mcmc -order libfm, -method als); ") +
+                                     (vb ? "-method vb (online VB)" : "-method mcmc -order sbpmf (the SBPMF sampler)") +
+                                     " does not read them, and without them the relations' features would be missing");
         if (rec && lfm) throw std::runtime_error(rec_refusal);
         if (recg && (lfm || biased)) throw std::runtime_error(recg_refusal);  // (a guest bias would need its own draw)
         if (method != "mcmc" && !vb && !als)
@@ -661,7 +668,30 @@ int main(int argc, char** argv) {
             if (sbmf_load_libfm_meta(cl.get("meta", "").c_str(), (uint32_t)na, meta.data(), &nmeta_groups) != SBMF_OK)
                 throw std::runtime_error(std::string("-meta: ") + sbmf_loader_error());
         }
-        if (lfm) parse_regular(cl.get("regular", ""), nmeta_groups, cfg.reg0, cfg.regw, cfg.regv, greg_w, greg_v);
+        // -relation (libfm.cpp:301-322): the block tables and the maps of the train / test cases
+        struct RelFiles {
+            sbmf_cases block{};
+            uint32_t *train_row = nullptr, *test_row = nullptr, *group = nullptr;
+            uint64_t n_train = 0, n_test = 0;
+            uint32_t G = 0;
+        };
+        std::vector<RelFiles> rels;
+        {
+            std::stringstream ss(cl.get("relation", ""));
+            std::string stem;
+            while (std::getline(ss, stem, ','))
+                if (!stem.empty()) {
+                    rels.emplace_back();
+                    RelFiles& r = rels.back();
+                    if (sbmf_load_libfm_relation(stem.c_str(), &r.block, &r.train_row, &r.n_train, &r.test_row, &r.n_test,
+                                                 &r.group, &r.G) != SBMF_OK)
+                        throw std::runtime_error(std::string("-relation ") + stem + ": " + sbmf_loader_error());
+                }
+        }
+        if (!rels.empty()) std::cout << "#relations: " << rels.size() << std::endl;
+        uint32_t ngroups = nmeta_groups;  // the joined groups: the main table's, then every relation's
+        for (const RelFiles& r : rels) ngroups += r.G ? r.G : 1;
+        if (lfm) parse_regular(cl.get("regular", ""), ngroups, cfg.reg0, cfg.regw, cfg.regv, greg_w, greg_v);
         std::vector<uint32_t> rec_ids;
         if (rec) {
             std::ifstream f(cl.get("rec_users", ""));
@@ -726,22 +756,27 @@ int main(int argc, char** argv) {
             // (inferred or given) item offset on
             if ((lfm || vb) && off) chk(sbmf_set_dims(ctx, off, 0));
         }
-        if (grouped) {
-            chk(sbmf_set_attr_groups(ctx, (uint32_t)meta.size(), meta.data()));
-            if (!greg_w.empty()) chk(sbmf_set_group_regular(ctx, nmeta_groups, greg_w.data(), greg_v.data()));
+        for (RelFiles& r : rels) {
+            chk(sbmf_add_relation(ctx, &r.block, r.train_row, r.n_train, r.test_row, r.n_test, r.group, r.G));
+            sbmf_free_relation(&r.block, &r.train_row, &r.test_row, &r.group);
         }
+        if (grouped) chk(sbmf_set_attr_groups(ctx, (uint32_t)meta.size(), meta.data()));
+        if ((grouped || !rels.empty()) && !greg_w.empty())
+            chk(sbmf_set_group_regular(ctx, ngroups, greg_w.data(), greg_v.data()));
         chk(sbmf_prepare(ctx));
         uint32_t nu, ni;
         uint64_t ntr, nte;
         chk(sbmf_get_dims(ctx, &nu, &ni, &ntr, &nte));
-        if (grouped) {  // DataMetaInfo::debug (Data.h:63-68)
-            std::vector<uint32_t> cnt(nmeta_groups);
+        if (grouped || !rels.empty()) {  // DataMetaInfo::debug (Data.h:63-68) of the joined table
+            std::vector<uint32_t> cnt(ngroups);
+            uint32_t na = (uint32_t)meta.size();
             chk(sbmf_get_fm_groups(ctx, nullptr, cnt.data(), nullptr, nullptr, nullptr, nullptr));
-            std::cout << "#attr=" << meta.size() << "\t#groups=" << nmeta_groups << std::endl;
-            for (uint32_t g = 0; g < nmeta_groups && cl.getl("verbosity", 0) > 0; ++g)
+            if (!rels.empty()) chk(sbmf_fm_info(ctx, &na, nullptr, nullptr));
+            std::cout << "#attr=" << na << "\t#groups=" << ngroups << std::endl;
+            for (uint32_t g = 0; g < ngroups && cl.getl("verbosity", 0) > 0; ++g)
                 std::cout << "#attr_in_group[" << g << "]=" << cnt[g] << std::endl;
         }
-        if (!general && grouped) {  // the triples through the general learner
+        if (!general && (grouped || !rels.empty())) {  // the triples through the general learner
             uint32_t na = 0, nr = 0;
             chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
             std::cout << "#users=" << nu << "\t#items=" << ni << "\t#attributes=" << na << "\t#ranges=" << nr
@@ -764,7 +799,7 @@ int main(int argc, char** argv) {
         rs.vb = vb;
         rs.lfm = lfm;
         rs.cls = cls;
-        rs.G = grouped ? nmeta_groups : 1;
+        rs.G = grouped || !rels.empty() ? ngroups : 1;
         rs.k1 = dim[1] != 0;
         rs.K = cfg.num_factor;
         rs.ctx = ctx;

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -103,6 +103,63 @@ class Cases:
         c.ptr, c.attr = _ptr(self.ptr, C.c_uint64), _ptr(self.attr, C.c_uint32)
         c.x, c.target = _ptr(self.x, C.c_float), _ptr(self.target, C.c_float)
         return c
+
+
+class Relation:
+    """A block-structure relation (libFM's -relation; sbmf_add_relation): ``block`` is the block
+    table as Cases (one row per block row, targets ignored), ``train_row`` / ``test_row`` the block
+    row every train / test case joins, ``group`` the relation's own attribute groups ([block.num_attr],
+    libFM's <stem>.groups) or None for one group."""
+
+    def __init__(self, block, train_row, test_row=(), group=None):
+        if not isinstance(block, Cases):
+            raise ValueError("block must be Cases")
+        self.block = block
+        self.train_row, self.test_row = _u32(train_row).ravel(), _u32(test_row).ravel()
+        self.group = None if group is None else _u32(group).ravel()
+        if self.group is not None and len(self.group) != block.num_attr:
+            raise ValueError("group must hold block.num_attr = %d ids; %d given" % (block.num_attr, len(self.group)))
+
+    @property
+    def num_groups(self):
+        return int(self.group.max()) + 1 if self.group is not None and len(self.group) else 1
+
+
+def load_libfm_relation(stem):
+    """libFM's relation files <stem>.xt (or .x), <stem>.train, <stem>.test and the optional
+    <stem>.groups as a Relation (sbmf_load_libfm_relation)."""
+    c, G = _lib.CasesC(), C.c_uint32()
+    tr, te, g = (C.POINTER(C.c_uint32)() for _ in range(3))
+    ntr, nte = C.c_uint64(), C.c_uint64()
+    rc = lib.sbmf_load_libfm_relation(str(stem).encode(), C.byref(c), C.byref(tr), C.byref(ntr), C.byref(te),
+                                      C.byref(nte), C.byref(g), C.byref(G))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_loader_error().decode())
+    try:
+        arr = lambda p, m, t: np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, t)
+        n, nnz = int(c.n), int(c.nnz)
+        block = Cases(arr(c.ptr, n + 1, np.uint64), arr(c.attr, nnz, np.uint32), arr(c.x, nnz, np.float32),
+                      np.zeros(n, np.float32), num_attr=int(c.num_attr))
+        return Relation(block, arr(tr, ntr.value, np.uint32), arr(te, nte.value, np.uint32),
+                        arr(g, int(c.num_attr), np.uint32) if g else None)
+    finally:
+        lib.sbmf_free_relation(C.byref(c), C.byref(tr), C.byref(te), C.byref(g))
+
+
+def save_libfm_relation(stem, relation, binary_maps=False):
+    """Write <stem>.x (the block table, row-major: libFM's transpose tool makes the .xt its MCMC / ALS
+    learner reads), <stem>.train / <stem>.test (text, or binary DVector<uint>) and, when the relation has
+    groups, <stem>.groups."""
+    c = relation.block._c()
+    rc = lib.sbmf_save_libfm_block((str(stem) + ".x").encode(), C.byref(c))
+    for ext, m in ((".train", relation.train_row), (".test", relation.test_row)):
+        if rc == SBMF_OK:
+            rc = lib.sbmf_save_libfm_row_map((str(stem) + ext).encode(), _ptr(m, C.c_uint32), len(m), 1 if binary_maps else 0)
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_loader_error().decode())
+    if relation.group is not None:
+        with open(str(stem) + ".groups", "w") as f:
+            f.write("".join("%d\n" % x for x in relation.group))
 
 
 def load_libfm_cases(path):
@@ -323,7 +380,7 @@ class FMLearnSBPMF:
         else:
             self.cfg.method = METHOD_LIBFM_MCMC if order == "libfm" else METHOD_MCMC
         self.cfg.libfm_dim = (1 if k0 else 0) | (2 if k1 else 0)
-        self._regular, self._groups = regular, None
+        self._regular, self._groups, self._relations = regular, None, []
         if np.ndim(regular) == 0 or len(regular) <= 3:  # the 1 + 2G form waits for set_groups
             self.cfg.reg0, self.cfg.regw, self.cfg.regv = parse_regular(regular)[:3]
         self.cfg.vb_batches = vb_batches
@@ -382,9 +439,39 @@ class FMLearnSBPMF:
         if self.ctx is not None:
             self._send_groups()
 
+    def add_relation(self, relation):
+        """libFM's -relation: register a Relation, in -relation order, before set_data.  Its
+        attributes follow the main table's ids and its groups the main table's groups; fm(),
+        fm_info() and fm_groups() then speak of the joined spaces (fm_relation_info() has the
+        offsets) and ``regular`` in its per-group form takes 1 + 2G values over all groups."""
+        if not isinstance(relation, Relation):
+            raise ValueError("add_relation takes a Relation")
+        if self._train is not None:
+            raise SBMFError(SBMF_E_STATE, "add_relation: the data is already set")
+        self._relations.append(relation)
+
+    def _send_relations(self):
+        for r in self._relations:
+            c = r.block._c()
+            g = r.group
+            self._check(lib.sbmf_add_relation(self.ctx, C.byref(c), _ptr(r.train_row, C.c_uint32), len(r.train_row),
+                                              _ptr(r.test_row, C.c_uint32), len(r.test_row),
+                                              _ptr(g, C.c_uint32) if g is not None else None,
+                                              r.num_groups if g is not None else 0))
+
+    def fm_relation_info(self):
+        """sbmf_fm_relation_info: one dict per relation -- attr_offset, num_attr, block_rows, nranges,
+        group_offset, num_groups."""
+        n = C.c_uint32()
+        self._check(lib.sbmf_fm_relation_info(self.ctx, C.byref(n), 0, None, None, None, None, None, None))
+        a = [np.zeros(max(n.value, 1), np.uint32) for _ in range(6)]
+        self._check(lib.sbmf_fm_relation_info(self.ctx, C.byref(n), n.value, *[_ptr(x, C.c_uint32) for x in a]))
+        keys = ("attr_offset", "num_attr", "block_rows", "nranges", "group_offset", "num_groups")
+        return [{k: int(x[r]) for k, x in zip(keys, a)} for r in range(n.value)]
+
     def _send_groups(self):
         g = self._groups
-        G = int(g.max()) + 1 if g is not None else 1
+        G = (int(g.max()) + 1 if g is not None else 1) + sum(r.num_groups for r in self._relations)
         r0, rw, rv, gw, gv = parse_regular(self._regular, G)
         if self.ctx is None:  # the context is created with reg0 (the per-group values go to it below)
             self.cfg.reg0, self.cfg.regw, self.cfg.regv = r0, rw, rv
@@ -407,8 +494,14 @@ class FMLearnSBPMF:
         return {"G": n, "cnt": cnt, "w_lambda": wl, "w_mu": wm, "v_lambda": vl, "v_mu": vm}
 
     def set_data(self, train, test=None, num_users=0, num_items=0):
-        if self._groups is not None or not (np.ndim(self._regular) == 0 or len(self._regular) <= 3):
+        grouped = self._groups is not None or not (np.ndim(self._regular) == 0 or len(self._regular) <= 3)
+        # relations are checked against the data, and the per-group -regular counts their groups:
+        # with relations the groups go after them, else before the data as always
+        if grouped and not self._relations:
             self._send_groups()
+        if self._relations and self.ctx is None:
+            G = (int(self._groups.max()) + 1 if self._groups is not None else 1) + sum(r.num_groups for r in self._relations)
+            self.cfg.reg0, self.cfg.regw, self.cfg.regv = parse_regular(self._regular, G)[:3]
         self.init()
         self._train, self._test = train, test
         if isinstance(train, Cases):  # libFM order / ALS: cases with any number of features
@@ -419,15 +512,17 @@ class FMLearnSBPMF:
             if test is not None:
                 c = test._c()
                 self._check(lib.sbmf_set_test_cases(self.ctx, C.byref(c)))
-            self._check(lib.sbmf_prepare(self.ctx))
-            return
-        self._check(lib.sbmf_set_train(self.ctx, train.num_cases, _ptr(train.user, C.c_uint32),
-                                       _ptr(train.item, C.c_uint32), _ptr(train.rating, C.c_double)))
-        if test is not None:
-            self._check(lib.sbmf_set_test(self.ctx, test.num_cases, _ptr(test.user, C.c_uint32),
-                                          _ptr(test.item, C.c_uint32), _ptr(test.rating, C.c_double)))
-        if num_users or num_items:
-            self._check(lib.sbmf_set_dims(self.ctx, num_users, num_items))
+        else:
+            self._check(lib.sbmf_set_train(self.ctx, train.num_cases, _ptr(train.user, C.c_uint32),
+                                           _ptr(train.item, C.c_uint32), _ptr(train.rating, C.c_double)))
+            if test is not None:
+                self._check(lib.sbmf_set_test(self.ctx, test.num_cases, _ptr(test.user, C.c_uint32),
+                                              _ptr(test.item, C.c_uint32), _ptr(test.rating, C.c_double)))
+            if num_users or num_items:
+                self._check(lib.sbmf_set_dims(self.ctx, num_users, num_items))
+        if self._relations:
+            self._send_relations()
+            self._send_groups()
         self._check(lib.sbmf_prepare(self.ctx))
 
     # -- fm_learn::learn(train, test) (fm_learn.h:150; fm_learn_mcmc.h:1154)

@@ -145,6 +145,14 @@ SIGNATURES = {
     "sbmf_set_group_regular": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
     "sbmf_get_fm_groups": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_F64, _P_F64, _P_F64, _P_F64]),
     "sbmf_load_libfm_meta": (C.c_int, [C.c_char_p, C.c_uint32, _P_U32, _P_U32]),
+    "sbmf_add_relation": (C.c_int, [C.c_void_p, C.POINTER(CasesC), _P_U32, C.c_uint64, _P_U32, C.c_uint64, _P_U32,
+                                    C.c_uint32]),
+    "sbmf_load_libfm_relation": (C.c_int, [C.c_char_p, C.POINTER(CasesC), C.POINTER(_P_U32), C.POINTER(C.c_uint64),
+                                           C.POINTER(_P_U32), C.POINTER(C.c_uint64), C.POINTER(_P_U32), _P_U32]),
+    "sbmf_free_relation": (None, [C.POINTER(CasesC), C.POINTER(_P_U32), C.POINTER(_P_U32), C.POINTER(_P_U32)]),
+    "sbmf_save_libfm_block": (C.c_int, [C.c_char_p, C.POINTER(CasesC)]),
+    "sbmf_save_libfm_row_map": (C.c_int, [C.c_char_p, _P_U32, C.c_uint64, C.c_int]),
+    "sbmf_fm_relation_info": (C.c_int, [C.c_void_p, _P_U32, C.c_uint32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32]),
     "sbmf_test_fm_group_sums": (C.c_int, [C.c_void_p, _P_F64]),
     "sbmf_test_tgauss": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, _P_F64,
                                    C.POINTER(C.c_int32), _P_U32, _P_F64]),
