@@ -319,9 +319,10 @@ int sbmf_get_timing(sbmf_ctx* ctx, sbmf_timing* t);
  * draws bit for bit what it draws without one.
  * Scope: the SBPMF sampler (SBMF_METHOD_MCMC, every quirk set) on one rank.
  * Out of scope here, each refused with SBMF_E_STATE and a message naming the
- * reason: the VB, libFM-MCMC and ALS learners; a context that joined a
- * communicator; a virtual rank; and reading results before any sweep was
- * accumulated.
+ * reason: the VB, libFM-MCMC and ALS learners (the libFM learners have a list
+ * of their own over a relation's block rows: sbmf_fm_query_cases below); a
+ * context that joined a communicator; a virtual rank; and reading results
+ * before any sweep was accumulated.
  *
  * sbmf_watch_users: register (or replace) the list.  After sbmf_prepare, also
  * between sbmf_run calls.  Allocates and zeroes two [n][Jp] f64 accumulators
@@ -651,6 +652,68 @@ void sbmf_free_relation(sbmf_cases* block, uint32_t** train_row, uint32_t** test
 int sbmf_save_libfm_block(const char* path, const sbmf_cases* block);
 int sbmf_save_libfm_row_map(const char* path, const uint32_t* row, uint64_t n, int binary);
 
+/* --- query list: posterior top-N of query cases over a relation's block rows ---------------- */
+/* Not a reference interface: bin/libFM scores the test cases it was given.  For
+ * libFM's MCMC / ALS learner (SBMF_METHOD_LIBFM_MCMC, SBMF_METHOD_ALS) with
+ * relations, a query list names one relation R, the candidates, and n query
+ * cases; every query holds main-table features and joins one block row of every
+ * other relation.  After each iteration the learner adds, for every query q and
+ * every block row j of R, libFM's prediction of "q joined to j" and its square to
+ * two device-resident [n][nBp] f64 tables (nBp = R's block rows rounded up to 16):
+ *   score(q, j) = ((w0 + a_q) + y_j) + sum_f s_q[f] * qB_R[j][f]
+ *   s_q[f] = sum over q's entries of v[attr][f] x + sum_{r != R} qB_r[rows[r][q]][f]
+ *   a_q    = sum_f 1/2 s_q[f]^2 - sum_f sum_entries 1/2 v^2 x^2 + sum_entries w x
+ *            + sum_{r != R} qs_r[rows[r][q]]
+ * with qB_r[j][f] = sum over block row j's entries of v x, qs_r[j] = - sum_f sum
+ * 1/2 v^2 x^2 + sum w x and y_j = sum_f 1/2 qB_R[j][f]^2 + qs_R[j]: the model's
+ * prediction with the square 1/2 (s + qB)^2 multiplied out (w0 / w only with the
+ * -dim flags k0 / k1).  Regression adds the score, clamped to the train targets'
+ * [min, max] with flags bit 0 as the test prediction is; classification adds the
+ * probability cdf_gaussian(score) (flags bit 0 has no effect).  All in f64, every
+ * element summed in a fixed order without atomics: a rerun gives the same bits.
+ * The chain is untouched: w0, w, v, the hyperparameters and the predictions are
+ * bit for bit what they are without a list, and a context without a list launches
+ * what it launched before this interface existed.
+ * MCMC: the tables hold every iteration run since registration (libFM's sum_all
+ * has no burn-in; registering between sbmf_run calls skips early iterations).
+ * ALS: the result is the latest iteration's model, as its predictions are -- the
+ * tables are overwritten, the count is 1 and stdev reads back as exactly 0.
+ * Memory: 16 n nBp bytes for the tables, plus the operand copies ((n + n_B) (Kp + 1)
+ * doubles, Kp = K rounded up to 16) and the queries.
+ *
+ * sbmf_fm_query_cases: register (or replace, zeroing the tables and the count)
+ * the list, after sbmf_prepare, also between sbmf_run calls; queries->n = 0 drops
+ * it and frees everything.  queries: a CSR of main-table features (ids below
+ * attr_offset_0 of sbmf_fm_relation_info; a query may have none; targets ignored).
+ * rows: [nrel] arrays of [n] block-row indices; rows[relation] is ignored and may
+ * be NULL (rows itself may be NULL with one relation).  excl_ptr[n + 1] /
+ * excl_rows: a CSR of the block rows left out of query q's top-N (both NULL:
+ * none).  flags bit 0: clamp.
+ * SBMF_E_STATE, with a message naming the reason: a context of another method
+ * (the SBPMF sampler, VB), one that joined a communicator or is a virtual rank,
+ * one not prepared, one without relations; reading results before any iteration
+ * ran.  SBMF_E_ARG: relation not below the number of relations; an attribute id
+ * at or above attr_offset_0; a block row at or above its relation's count; a
+ * missing rows[r], r != relation; an exclusion row out of range or a decreasing
+ * excl_ptr; unknown flags.  SBMF_E_NOMEM with the byte count in the message (the
+ * list is then dropped). */
+int sbmf_fm_query_cases(sbmf_ctx* ctx, uint32_t relation, const sbmf_cases* queries, const uint32_t* const* rows,
+                        const uint32_t* excl_ptr, const uint32_t* excl_rows, uint32_t flags);
+/* Query q's row of posterior means and population standard deviations over the
+ * iterations accumulated, one value per block row of the candidates' relation
+ * ([n_B]); definitions as sbmf_watch_scores.  stdev may be NULL. */
+int sbmf_fm_query_scores(sbmf_ctx* ctx, uint32_t q, double* mean, double* stdev);
+/* sbmf_recommend over the block rows: per query the topn (1..1024) rows with the
+ * largest mean - risk * stdev, ties by ascending row; the query's excluded rows
+ * are left out unless flags bit 0 is set.  rows / mean / stdev: [n][topn]; empty
+ * slots hold 0xffffffff and NaN.  stdev may be NULL. */
+int sbmf_fm_query_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* rows, double* mean,
+                            double* stdev);
+/* Device time (HIP events), ms, of the last iteration's query terms and operand
+ * copy (two launches), of its scoring launch, and of the last selection; 0 before
+ * the first. */
+int sbmf_fm_query_timing(sbmf_ctx* ctx, double* ms_terms, double* ms_score, double* ms_select);
+
 /* --- multi-GPU layout (host only) ---------------------------------------------------------- */
 /* The row partition every rank uses: contiguous row blocks balanced by
  * ratings (ptr = CSR/CSC offsets [R+1]), boundaries rounded to 256 rows.
@@ -740,6 +803,9 @@ int sbmf_test_fm_group_sums(sbmf_ctx* ctx, double* out);
  * i (`it`, `index` and `device` unused). */
 int sbmf_test_tgauss(int mode, int device, uint64_t seed, uint32_t it, uint64_t n, const double* mean,
                      const int32_t* sign, const uint32_t* index, double* out);
+/* The shape the lists' scoring launch takes for factor rows of Kp values (needs no GPU): the
+ * rows of the list one workgroup holds in LDS, and the bytes of dynamic LDS it asks for. */
+int sbmf_test_watch_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
 
 #ifdef __cplusplus
 }

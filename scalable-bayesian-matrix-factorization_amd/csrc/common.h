@@ -100,6 +100,9 @@ struct DBuf {
         hipError_t e = hipMalloc(&p, b);
         if (e != hipSuccess) {
             p = nullptr;
+            // a refused allocation is reported here and is no fault of the device: take it off the
+            // thread's last-error slot, or the next launch's hipGetLastError() would return it
+            (void)hipGetLastError();
             fail(SBMF_E_NOMEM, "hipMalloc(%zu) failed: %s", b, hipGetErrorString(e));
         }
         bytes = b;

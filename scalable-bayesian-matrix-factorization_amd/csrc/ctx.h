@@ -26,6 +26,7 @@
 #include "fmc.h"
 #include "fmm.h"
 #include "fmg.h"
+#include "fmq.h"
 #include "foldin.h"
 #include "recommend.h"
 #include "vbo.h"
@@ -98,17 +99,20 @@ struct Hyper {
 // A score list: for each of n rows of a factor table (watched users; fold-in guests) the running
 // first / second moments of its scores against every item, [n][Jp] doubles each, added to after
 // every collected sweep and read back as mean / spread or a top-N selection (recommend.hip).
+// The libFM learner's query list (fmq.h) keeps the same sums over the candidates' block rows: the
+// columns are the list's own count J, not the context's items.
 // Nothing here exists while no list is registered (n == 0).
 struct ScoreList {
-    const char* what;      // "watch list" / "fold-in list" in messages
+    const char* what;      // "watch list" / "fold-in list" / "query list" in messages
     const char* reg;       // the registering entry point
-    uint32_t n = 0, Jp = 0;
+    uint32_t n = 0, J = 0, Jp = 0;  // rows, columns, columns rounded up to 16
     uint32_t count = 0;    // sweeps accumulated since the list was registered
     int clamp = 0;         // flags bit 0: scores clamped like the test prediction
+    bool latest = false;   // the sums hold one sample, the latest (ALS): the spread reads back as exactly 0
     DBuf d_ids, d_S1, d_S2;  // the rows' indices in their table (the watched users, or 0..n-1); the sums
     hipEvent_t sel[2] = {};  // the last selection [begin, end]
     bool timed_select = false;
-    void alloc(uint32_t n_, uint32_t J, int clamp_, hipStream_t st);  // sums zeroed; d_ids is the caller's to fill
+    void alloc(uint32_t n_, uint32_t J_, int clamp_, hipStream_t st);  // sums zeroed; d_ids is the caller's to fill
     void drop();
     template <typename T>
     void accumulate(sbmf_ctx* c, const T* rows, const double* bu, const double* bv, double b0, hipStream_t se);
@@ -254,6 +258,11 @@ struct sbmf_ctx {
     // hyper copy done = draw begin, draw end = scoring begin (recorded once fdrawn > 0), scoring
     // end (once guests.count > 0)
     hipEvent_t fev[3] = {};
+    // Query list of the libFM learner (sbmf_fm_query_cases): the sums over the candidates' block
+    // rows (fmq.d_ids is 0..n-1), and what the learner reads and writes each iteration (fmq.h; fm->query
+    // points at it while a list is registered).  Nothing here exists while no list is registered.
+    ScoreList fmq{"query list", "sbmf_fm_query_cases"};
+    FMQueryList fmqd;
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
     // -method mcmc --order libfm / als: libFM's chain (fmc.cpp) on triples (fmm.cpp) or on cases
     // with any number of features (fmg.cpp).  ctr / cte: the host copies of sbmf_set_train_cases /

@@ -287,6 +287,7 @@ void FMChain::run(uint32_t iters, sbmf_sweep_cb cb, void* user) {
             HIPCHK(launch_sum_cols(d_tpart.as<double>(), (uint32_t)((T + 255) / 256), 2, res + 3, st));
             n_launch += 2;
         }
+        if (query) score_queries();
         HIPCHK(hipEventRecord(ev[2], st));
         double h[3] = {0, 0, 0};
         HIPCHK(hipMemcpyAsync(h, res + 2, sizeof h, hipMemcpyDeviceToHost, st));
@@ -350,6 +351,7 @@ void FMChain::evaluate_class(sbmf_sweep_info& info) {
         ++n_launch;
         HIPCHK(hipStreamSynchronize(st));  // t is a local
     }
+    if (query) score_queries();
     HIPCHK(hipEventRecord(ev[2], st));
     unsigned long long h[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(h, cres, sizeof h, hipMemcpyDeviceToHost, st));

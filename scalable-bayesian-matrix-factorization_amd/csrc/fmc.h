@@ -40,6 +40,8 @@
 
 namespace sbmf {
 
+struct FMQueryList;
+
 struct FMChain {
     sbmf_config cfg{};
     uint32_t K = 0, Kp = 0, p = 0;  // p: libFM's num_attribute
@@ -107,6 +109,11 @@ struct FMChain {
     virtual void class_train(FMTargetArgs ta) = 0;
     virtual void class_test(double it1, uint32_t* cnt, double* ll) = 0;
     virtual void sub_targets(const double* t) = 0;
+    // the query list (fmq.h; the general learner with relations): this iteration's scores of the
+    // registered queries into the list's sums, last in the evaluate step.  query null: no list --
+    // nothing is launched or recorded.
+    FMQueryList* query = nullptr;
+    virtual void score_queries() {}
 
     // ---- what the chain does
     // the shared set-up, last in a learner's create (its data uploaded): the flags, the target

@@ -18,7 +18,9 @@
 
 #include "common.h"
 #include "fmc.h"
+#include "fmq.h"
 #include "kernels.h"
+#include "recommend.h"
 
 namespace sbmf {
 
@@ -280,6 +282,42 @@ struct FGLearner : FMChain {
         HIPCHK(fmg_class_test(predict_args(false), it1, d_pthis.as<double>(), d_sum.as<double>(), cnt, ll, st));
     }
     void sub_targets(const double* t) override { HIPCHK(fmg_sub_targets(d_eq.as<double2>(), N, t, st)); }
+    // The query list's three launches (fmq.h), after the frames: the block rows' terms are this
+    // model's.  MCMC adds the iteration to the sums; ALS, whose result is the latest model (as its
+    // predictions are), writes them and keeps the count at 1.
+    void score_queries() override {
+        FMQueryList& ql = *query;
+        block_predict();
+        FMQTermsArgs t{};
+        t.nq = ql.nq;
+        t.ptr = ql.d_ptr.as<uint32_t>();
+        t.attr = ql.d_attr.as<uint32_t>();
+        t.x = ql.d_x.as<float>();
+        t.vT = d_vT.as<double>();
+        t.w = d_w.as<double>();
+        t.K = K;
+        t.Kp = Kp;
+        t.k1 = k1;
+        for (uint32_t r = 0; r < rels.size(); ++r) {
+            if (r == ql.rel) continue;
+            t.rel[t.nrel++] = {ql.d_rows.as<uint32_t>() + (size_t)r * ql.nq, rels[r]->d_qbf.as<double>(),
+                               rels[r]->d_qs.as<double>()};
+        }
+        t.s = ql.d_s.as<double>();
+        t.a = ql.d_a.as<double>();
+        const FGRel& R = *rels[ql.rel];
+        HIPCHK(hipEventRecord(ql.ev[0], st));
+        HIPCHK(fmq_terms(t, st));
+        HIPCHK(fmq_operands(R.d_qbf.as<double>(), R.d_rb.as<double4>(), R.nb, K, Kp, ql.d_B.as<double>(),
+                            ql.d_y.as<double>(), st));
+        HIPCHK(hipEventRecord(ql.ev[1], st));
+        const int epi = (classify() ? WATCH_EPI_CDF : 0) | (do_sample ? 0 : WATCH_EPI_SET);
+        HIPCHK(launch_watch_accum_epi(epi, ql.ids, ql.nq, t.s, ql.d_B.as<double>(), R.nb, Kp, t.a, ql.d_y.as<double>(),
+                                      k0 ? w0 : 0.0, classify() ? 0 : ql.clamp, lo, hi, ql.S1, ql.S2, st));
+        HIPCHK(hipEventRecord(ql.ev[2], st));
+        *ql.count = do_sample ? *ql.count + 1 : 1;
+        n_launch += 3;
+    }
     void residual_sums(double* s) override {
         double* res = d_res.as<double>();
         HIPCHK(fmg_esums(d_eq.as<double2>(), N, w0, d_part.as<double>(), st));

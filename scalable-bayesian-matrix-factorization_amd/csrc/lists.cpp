@@ -1,9 +1,11 @@
 // lists.cpp -- the score lists (ScoreList, ctx.h) and their entry points: the watch list
-// (sbmf_watch_*, sbmf_recommend) and the fold-in list (sbmf_foldin_*).
+// (sbmf_watch_*, sbmf_recommend), the fold-in list (sbmf_foldin_*) and the libFM learner's query
+// list (sbmf_fm_query_*, fmq.h).
 #include "ctx.h"
 
-void ScoreList::alloc(uint32_t n_, uint32_t J, int clamp_, hipStream_t st) {
+void ScoreList::alloc(uint32_t n_, uint32_t J_, int clamp_, hipStream_t st) {
     n = n_;
+    J = J_;
     Jp = sbmf::watch_jp(J);
     clamp = clamp_;
     const size_t bytes = (size_t)n * Jp * sizeof(double);
@@ -17,8 +19,9 @@ void ScoreList::alloc(uint32_t n_, uint32_t J, int clamp_, hipStream_t st) {
 void ScoreList::drop() {
     for (sbmf::DBuf* d : {&d_ids, &d_S1, &d_S2}) d->release();
     for (hipEvent_t& e : sel) sbmf::event_destroy(e);
-    n = Jp = count = 0;
+    n = J = Jp = count = 0;
     clamp = 0;
+    latest = false;
     timed_select = false;
 }
 // this sample's scores of the list's rows of `rows` (a factor table: U, or the guests' G) against
@@ -34,7 +37,6 @@ template void ScoreList::accumulate<float>(sbmf_ctx*, const float*, const double
 template void ScoreList::accumulate<double>(sbmf_ctx*, const double*, const double*, const double*, double, hipStream_t);
 void ScoreList::scores(sbmf_ctx* c, const char* fn, uint32_t row, double* mean, double* stdev) {
     if (row >= n) sbmf::fail(SBMF_E_ARG, "%s: row %u of a %s of %u", fn, row, what, n);
-    const uint32_t J = c->J;
     sbmf::DBuf tmp;
     tmp.alloc((size_t)2 * J * sizeof(double));
     double* d = tmp.as<double>();
@@ -43,12 +45,13 @@ void ScoreList::scores(sbmf_ctx* c, const char* fn, uint32_t row, double* mean, 
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
     if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev && latest) std::fill(stdev, stdev + J, 0.0);
 }
 // top-N of every row; "rated" items (flags bit 0 clear: left out) are those of the rows' CSR --
 // the user side's for watched users, the guest CSR for guests
 void ScoreList::recommend(sbmf_ctx* c, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn,
                           uint32_t flags, double risk, uint32_t* items, double* mean, double* stdev) {
-    const uint32_t J = c->J, Jw = sbmf::watch_jw(J);
+    const uint32_t Jw = sbmf::watch_jw(J);
     const size_t slots = (size_t)n * topn;
     sbmf::DBuf d_it, d_ms, d_mask;
     d_it.alloc(slots * sizeof(uint32_t));
@@ -70,6 +73,9 @@ void ScoreList::recommend(sbmf_ctx* c, const uint32_t* csr_ptr, const uint32_t* 
     HIPCHK(hipMemcpy(items, d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(mean, d_ms.p, slots * sizeof(double), hipMemcpyDeviceToHost));
     if (stdev) HIPCHK(hipMemcpy(stdev, d_ms.as<double>() + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev && latest)  // one sample: no spread (the empty slots keep their NaN)
+        for (size_t q = 0; q < slots; ++q)
+            if (items[q] != 0xffffffffu) stdev[q] = 0.0;
 }
 
 extern "C" {
@@ -310,6 +316,204 @@ int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double*
         if (ms_score && ctx->guests.count) *ms_score = sbmf::ev_ms(ctx->fev[1], ctx->fev[2]);
     }
     if (ms_select) *ms_select = ctx->guests.timed_select ? sbmf::ev_ms(ctx->guests.sel[0], ctx->guests.sel[1]) : 0.0;
+    API_END(ctx)
+}
+
+// --- query list of libFM's MCMC / ALS learner ---------------------------------------------------
+static void fmq_drop(sbmf_ctx* c) {
+    if (c->fm) c->fm->query = nullptr;
+    c->fmq.drop();
+    c->fmqd.drop();
+}
+// The contexts the query list covers: the general libFM learner with relations, on one rank.
+static void fmq_scope(const sbmf_ctx* c, const char* fn) {
+    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no query list there", fn);
+    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
+        sbmf::fail(SBMF_E_STATE, "%s: the query list runs on one rank; this context joined a communicator", fn);
+    if (c->cfg.method != SBMF_METHOD_LIBFM_MCMC && c->cfg.method != SBMF_METHOD_ALS)
+        sbmf::fail(SBMF_E_STATE, "%s: the query list is offered by libFM's MCMC / ALS learner (SBMF_METHOD_LIBFM_MCMC, "
+                                 "SBMF_METHOD_ALS) only; this context runs the %s (its lists: sbmf_watch_users, "
+                                 "sbmf_foldin_users)", fn, c->cfg.method == SBMF_METHOD_VB ? "online VB learner" : "SBPMF sampler");
+    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+    if (!c->fm || c->fm->rel_info.empty())
+        sbmf::fail(SBMF_E_STATE, "%s: this context has no relations (sbmf_add_relation): the candidates of a query "
+                                 "list are the block rows of one", fn);
+}
+
+int sbmf_fm_query_cases(sbmf_ctx* ctx, uint32_t relation, const sbmf_cases* queries, const uint32_t* const* rows,
+                        const uint32_t* excl_ptr, const uint32_t* excl_rows, uint32_t flags) {
+    API_BEGIN
+    const char* fn = "sbmf_fm_query_cases";
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    if (!queries) sbmf::fail(SBMF_E_ARG, "%s: null queries", fn);
+    fmq_scope(ctx, fn);
+    sbmf::FMChain& fm = *ctx->fm;
+    const uint32_t nrel = (uint32_t)fm.rel_info.size();
+    if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "%s: unknown flags 0x%x (bit 0 = clamp)", fn, flags & ~1u);
+    if (relation >= nrel)
+        sbmf::fail(SBMF_E_ARG, "%s: relation %u is not below the context's %u relations", fn, relation, nrel);
+    if (queries->n == 0) {
+        list_sync(ctx);
+        fmq_drop(ctx);
+        return SBMF_OK;
+    }
+    if (queries->n >= 0xfffffffeull || queries->nnz >= 0xffffffffull)
+        sbmf::fail(SBMF_E_ARG, "%s: %llu queries with %llu features are too many", fn, (unsigned long long)queries->n,
+                   (unsigned long long)queries->nnz);
+    const uint32_t n = (uint32_t)queries->n, nnz = (uint32_t)queries->nnz;
+    if (!queries->ptr || (nnz && (!queries->attr || !queries->x))) sbmf::fail(SBMF_E_ARG, "%s: null array in queries", fn);
+    if (queries->ptr[0] != 0 || queries->ptr[n] != nnz) sbmf::fail(SBMF_E_ARG, "%s: queries ptr must run from 0 to nnz", fn);
+    for (uint32_t q = 0; q < n; ++q)
+        if (queries->ptr[q + 1] < queries->ptr[q] || queries->ptr[q + 1] > nnz)
+            sbmf::fail(SBMF_E_ARG, "%s: queries ptr decreases at query %u", fn, q);
+    const uint32_t p_main = fm.rel_info[0].attr_offset;
+    for (uint32_t k = 0; k < nnz; ++k)
+        if (queries->attr[k] >= p_main)
+            sbmf::fail(SBMF_E_ARG, "%s: attr[%u] = %u is not a main attribute id (below attr_offset_0 = %u); the "
+                                   "relations' features come from the block rows", fn, k, queries->attr[k], p_main);
+    for (uint32_t r = 0; r < nrel; ++r) {
+        if (r == relation) continue;
+        if (!rows || !rows[r])
+            sbmf::fail(SBMF_E_ARG, "%s: rows[%u] is missing: every query joins one block row of each relation but "
+                                   "the candidates' (%u)", fn, r, relation);
+        for (uint32_t q = 0; q < n; ++q)
+            if (rows[r][q] >= fm.rel_info[r].block_rows)
+                sbmf::fail(SBMF_E_ARG, "%s: rows[%u][%u] = %u is not below relation %u's %u block rows", fn, r, q,
+                           rows[r][q], r, fm.rel_info[r].block_rows);
+    }
+    const uint32_t nb = fm.rel_info[relation].block_rows;
+    if (nb == 0) sbmf::fail(SBMF_E_ARG, "%s: relation %u has no block rows", fn, relation);
+    if ((excl_rows && !excl_ptr) || (excl_ptr && !excl_rows && excl_ptr[n] != excl_ptr[0]))
+        sbmf::fail(SBMF_E_ARG, "%s: excl_ptr and excl_rows go together (both NULL: no exclusions)", fn);
+    uint32_t nex = 0;
+    if (excl_ptr) {
+        for (uint32_t q = 0; q < n; ++q)
+            if (excl_ptr[q + 1] < excl_ptr[q])
+                sbmf::fail(SBMF_E_ARG, "%s: excl_ptr decreases at query %u (%u then %u)", fn, q, excl_ptr[q], excl_ptr[q + 1]);
+        nex = excl_ptr[n] - excl_ptr[0];
+        for (uint32_t k = 0; k < nex; ++k)
+            if (excl_rows[excl_ptr[0] + k] >= nb)
+                sbmf::fail(SBMF_E_ARG, "%s: excl_rows[%u] = %u is not below relation %u's %u block rows", fn,
+                           excl_ptr[0] + k, excl_rows[excl_ptr[0] + k], relation, nb);
+    }
+    list_sync(ctx);
+    fmq_drop(ctx);
+    const uint32_t Kp = fm.Kp, nbp = sbmf::watch_jp(nb);
+    const size_t b_sum = (size_t)n * nbp * sizeof(double);
+    const size_t b_tot = 2 * b_sum + ((size_t)n * (Kp + 1) + nb) * sizeof(double) + sbmf::fmq_operand_bytes(nb, Kp) +
+                         ((size_t)2 * n + 2 + (size_t)nrel * n + nex) * sizeof(uint32_t) + (size_t)nnz * 8 + n * sizeof(uint32_t);
+    try {
+        hipStream_t st = ctx->st;
+        // the sums first: a list the device cannot hold fails here, before any host copy is made
+        ctx->fmq.alloc(n, nb, (int)(flags & 1u), st);
+        ctx->fmq.latest = ctx->cfg.method == SBMF_METHOD_ALS;
+        // the queries as the learner keeps its cases: entries in ascending attribute (stable)
+        std::vector<uint32_t> ptr(n + 1), attr(nnz), ident(n), hrows((size_t)nrel * n, 0), ord;
+        std::vector<float> x(nnz);
+        for (uint32_t q = 0; q <= n; ++q) ptr[q] = (uint32_t)queries->ptr[q];
+        for (uint32_t q = 0; q < n; ++q) {
+            ident[q] = q;
+            const uint32_t b = ptr[q], m = ptr[q + 1] - b;
+            ord.resize(m);
+            std::iota(ord.begin(), ord.end(), 0u);
+            std::stable_sort(ord.begin(), ord.end(),
+                             [&](uint32_t i, uint32_t j) { return queries->attr[b + i] < queries->attr[b + j]; });
+            for (uint32_t k = 0; k < m; ++k) {
+                attr[b + k] = queries->attr[b + ord[k]];
+                x[b + k] = queries->x[b + ord[k]];
+            }
+        }
+        for (uint32_t r = 0; r < nrel; ++r)
+            if (r != relation) std::copy(rows[r], rows[r] + n, hrows.begin() + (size_t)r * n);
+        sbmf::FMQueryList& ql = ctx->fmqd;
+        sbmf::upload(ctx->fmq.d_ids, ident, st);
+        sbmf::upload(ql.d_ptr, ptr, st);
+        sbmf::upload(ql.d_attr, attr, st);
+        sbmf::upload(ql.d_x, x, st);
+        sbmf::upload(ql.d_rows, hrows, st);
+        ql.d_s.alloc((size_t)n * Kp * sizeof(double));
+        ql.d_a.alloc((size_t)n * sizeof(double));
+        ql.d_B.alloc(sbmf::fmq_operand_bytes(nb, Kp));
+        ql.d_y.alloc((size_t)nb * sizeof(double));
+        if (nex) {
+            std::vector<uint32_t> ep(n + 1);
+            for (uint32_t q = 0; q <= n; ++q) ep[q] = excl_ptr[q] - excl_ptr[0];  // the device CSR starts at 0
+            sbmf::upload(ql.d_eptr, ep, st);
+            ql.d_erows.alloc((size_t)nex * sizeof(uint32_t));
+            HIPCHK(hipMemcpyAsync(ql.d_erows.p, excl_rows + excl_ptr[0], (size_t)nex * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));  // ep is a local
+        }
+        for (hipEvent_t& e : ql.ev) sbmf::event_create(&e);
+        HIPCHK(hipStreamSynchronize(st));  // the vectors are locals
+        ql.rel = relation;
+        ql.nq = n;
+        ql.nb = nb;
+        ql.clamp = (int)(flags & 1u);
+        ql.ids = ctx->fmq.d_ids.as<uint32_t>();
+        ql.S1 = ctx->fmq.d_S1.as<double>();
+        ql.S2 = ctx->fmq.d_S2.as<double>();
+        ql.count = &ctx->fmq.count;
+        fm.query = &ql;
+    } catch (const sbmf::Error& e) {
+        fmq_drop(ctx);
+        if (e.code == SBMF_E_NOMEM)
+            sbmf::fail(SBMF_E_NOMEM, "%s: %u queries against %u block rows need %zu bytes of device memory: %s", fn, n,
+                       nb, b_tot, e.msg.c_str());
+        throw;
+    } catch (...) {
+        fmq_drop(ctx);
+        throw;
+    }
+    API_END(ctx)
+}
+
+int sbmf_fm_query_scores(sbmf_ctx* ctx, uint32_t q, double* mean, double* stdev) {
+    API_BEGIN
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    fmq_scope(ctx, "sbmf_fm_query_scores");
+    list_ready(ctx, ctx->fmq, "sbmf_fm_query_scores", true, " (every iteration of sbmf_run accumulates one)");
+    ctx->fmq.scores(ctx, "sbmf_fm_query_scores", q, mean, stdev);
+    API_END(ctx)
+}
+
+int sbmf_fm_query_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, uint32_t* rows, double* mean,
+                            double* stdev) {
+    API_BEGIN
+    if (!ctx || !rows || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    fmq_scope(ctx, "sbmf_fm_query_recommend");
+    recommend_args("sbmf_fm_query_recommend", topn, flags, risk);
+    list_ready(ctx, ctx->fmq, "sbmf_fm_query_recommend", true, " (every iteration of sbmf_run accumulates one)");
+    // "rated": the query's exclusion list (none registered: nothing is left out)
+    if (!ctx->fmqd.d_eptr.p) flags |= 1u;
+    ctx->fmq.recommend(ctx, ctx->fmqd.d_eptr.as<uint32_t>(), ctx->fmqd.d_erows.as<uint32_t>(), topn, flags, risk, rows,
+                       mean, stdev);
+    API_END(ctx)
+}
+
+int sbmf_fm_query_timing(sbmf_ctx* ctx, double* ms_terms, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    fmq_scope(ctx, "sbmf_fm_query_timing");
+    list_registered(ctx->fmq, "sbmf_fm_query_timing");
+    if (ms_terms) *ms_terms = 0.0;
+    if (ms_score) *ms_score = 0.0;
+    if (ctx->fmq.count) {
+        list_sync(ctx);
+        if (ms_terms) *ms_terms = sbmf::ev_ms(ctx->fmqd.ev[0], ctx->fmqd.ev[1]);
+        if (ms_score) *ms_score = sbmf::ev_ms(ctx->fmqd.ev[1], ctx->fmqd.ev[2]);
+    }
+    if (ms_select) *ms_select = ctx->fmq.timed_select ? sbmf::ev_ms(ctx->fmq.sel[0], ctx->fmq.sel[1]) : 0.0;
+    API_END(ctx)
+}
+
+int sbmf_test_watch_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes) {
+    sbmf_ctx* ctx = nullptr;
+    API_BEGIN
+    if (!rows || !bytes) sbmf::fail(SBMF_E_ARG, "null argument");
+    const int mu = sbmf::watch_mu(Kp);
+    *rows = 16u * (uint32_t)mu;
+    *bytes = sbmf::watch_lds_bytes(mu, Kp);
     API_END(ctx)
 }
 

@@ -13,6 +13,13 @@ inline uint32_t watch_jp(uint32_t J) { return (J + 15) / 16 * 16; }
 // 32-bit words per row of the rated-item mask.
 inline uint32_t watch_jw(uint32_t J) { return (J + 31) / 32; }
 
+// The scoring launch's shape: a workgroup holds 16 MU rows in LDS, as many as 64 KB take (Kp <= 112:
+// 64, <= 240: 32, else 16), as rows of Kp + 2 doubles with their ids behind them.
+inline int watch_mu(uint32_t Kp) { return Kp <= 112 ? 4 : Kp <= 240 ? 2 : 1; }
+inline size_t watch_lds_bytes(int MU, uint32_t Kp) {
+    return (size_t)16 * MU * (Kp + 2) * sizeof(double) + 16 * MU * sizeof(uint32_t);
+}
+
 // One sweep's scores of the n watched users against all J items, added to the running sums:
 // s = U[users[w]] . V[j] (+ (b0 + bu[user]) + bv[j] when bu is non-null: the biased sampler),
 // clamped to [lo, hi] when clamp is set; S1[w][j] += s, S2[w][j] += s*s (rows of Jp doubles).
@@ -22,6 +29,16 @@ template <typename T>
 hipError_t launch_watch_accum(const uint32_t* users, uint32_t n, const T* U, const T* V, uint32_t J, uint32_t Kp,
                               const double* bu, const double* bv, double b0, int clamp, double lo, double hi,
                               double* S1, double* S2, hipStream_t st);
+
+// The same launch with an epilogue chosen by the caller, for f64 tables with both bias vectors
+// (the libFM query list, fmq.h: rows of A are the queries' s_q, rows of B the candidates' q^B, ba
+// = a_q, bb = y_j, b0 = w0): s = ((b0 + ba[row]) + bb[j]) + A[row] . B[j]; WATCH_EPI_CDF then
+// takes the probit probability ref_cdf_gaussian(s); WATCH_EPI_SET stores s and s * s in place of
+// adding them (the old sums are not read).  epi = 0 is launch_watch_accum<double>'s own kernel.
+enum : int { WATCH_EPI_CDF = 1, WATCH_EPI_SET = 2 };
+hipError_t launch_watch_accum_epi(int epi, const uint32_t* rows, uint32_t n, const double* A, const double* B,
+                                  uint32_t J, uint32_t Kp, const double* ba, const double* bb, double b0, int clamp,
+                                  double lo, double hi, double* S1, double* S2, hipStream_t st);
 
 // mean[j] = s1[j] / nw, sd[j] = sqrt(max(0, s2[j] / nw - mean[j]^2)) for j < J: one row's
 // moments, computed by the expressions the selection ranks by (bit for bit).

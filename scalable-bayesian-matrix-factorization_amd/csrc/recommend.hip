@@ -8,6 +8,8 @@
 
 #include <cmath>
 
+#include "rng.h"
+
 namespace sbmf {
 
 typedef double wd4 __attribute__((ext_vector_type(4)));
@@ -38,9 +40,13 @@ __device__ __forceinline__ void load4<float>(const float* p, double (&b)[4]) {
 // operands, a fixed permutation of the k order.  The padding columns of both tables are zero.
 // A tile's old sums are loaded before its K loop and added after it (0.41 -> 0.32 ms per launch
 // at ML-20M K=100, 1,024 users, together with the user groups along grid x).
+// EPI (recommend.h): what becomes of a score before it meets the sums.  0 is the watch and
+// fold-in lists' kernel; the libFM query list (fmq.h) adds WATCH_EPI_CDF -- the score's probit
+// probability, as fm_class_test_frame forms it -- and WATCH_EPI_SET -- the sums are written, not
+// added to, and the old ones never read (ALS: the latest model alone).
 constexpr uint32_t WATCH_TILES = 16;
 
-template <typename T, int MU>
+template <typename T, int MU, int EPI>
 __global__ __launch_bounds__(256) void k_watch_accum(const uint32_t* __restrict__ users, uint32_t n,
                                                      const T* __restrict__ U, const T* __restrict__ V, uint32_t J,
                                                      uint32_t Jp, uint32_t Kp, const double* __restrict__ bu,
@@ -69,16 +75,18 @@ __global__ __launch_bounds__(256) void k_watch_accum(const uint32_t* __restrict_
         for (int t = 0; t < MU; ++t) acc[t] = wd4{0, 0, 0, 0};
         // the old sums, asked for before the K loop so that they arrive under it
         double o1[MU][4], o2[MU][4];
+        if constexpr (!(EPI & WATCH_EPI_SET)) {
 #pragma unroll
-        for (int t = 0; t < MU; ++t)
+            for (int t = 0; t < MU; ++t)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t w = w0 + t * 16 + kq + 4 * j;
-                const bool ok = w < n && item < J;
-                const size_t o = ok ? (size_t)w * Jp + item : 0;
-                o1[t][j] = ok ? S1[o] : 0.0;
-                o2[t][j] = ok ? S2[o] : 0.0;
-            }
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t w = w0 + t * 16 + kq + 4 * j;
+                    const bool ok = w < n && item < J;
+                    const size_t o = ok ? (size_t)w * Jp + item : 0;
+                    o1[t][j] = ok ? S1[o] : 0.0;
+                    o2[t][j] = ok ? S2[o] : 0.0;
+                }
+        }
         for (uint32_t k0 = 0; k0 < Kp; k0 += 16) {
             double b[4];
             load4<T>(vp + k0, b);
@@ -101,38 +109,55 @@ __global__ __launch_bounds__(256) void k_watch_accum(const uint32_t* __restrict_
                 if (w >= n) continue;
                 double s = acc[t][j];
                 if (bu) s = ((b0 + bu[uid[r]]) + bj) + s;  // as k_test adds them
+                if constexpr (EPI & WATCH_EPI_CDF) s = ref_cdf_gaussian(s);
                 if (clamp) {
                     s = (s < hi) ? s : hi;
                     s = (lo < s) ? s : lo;
                 }
                 const size_t o = (size_t)w * Jp + item;
-                S1[o] = o1[t][j] + s;
-                S2[o] = o2[t][j] + s * s;
+                if constexpr (EPI & WATCH_EPI_SET) {
+                    S1[o] = s;
+                    S2[o] = s * s;
+                } else {
+                    S1[o] = o1[t][j] + s;
+                    S2[o] = o2[t][j] + s * s;
+                }
             }
     }
 }
 
-template <typename T, int MU>
+template <typename T, int MU, int EPI>
 static hipError_t watch_accum_mu(const uint32_t* users, uint32_t n, const T* U, const T* V, uint32_t J, uint32_t Kp,
                                  const double* bu, const double* bv, double b0, int clamp, double lo, double hi,
                                  double* S1, double* S2, hipStream_t st) {
     const uint32_t Jp = watch_jp(J);
     // the user groups along x: workgroups launched together read the same V rows
     const dim3 grid((n + 16 * MU - 1) / (16 * MU), (Jp / 16 + WATCH_TILES - 1) / WATCH_TILES);
-    const size_t lds = (size_t)16 * MU * (Kp + 2) * sizeof(double) + 16 * MU * sizeof(uint32_t);
-    k_watch_accum<T, MU><<<grid, 256, lds, st>>>(users, n, U, V, J, Jp, Kp, bu, bv, b0, clamp, lo, hi, S1, S2);
+    const size_t lds = watch_lds_bytes(MU, Kp);
+    k_watch_accum<T, MU, EPI><<<grid, 256, lds, st>>>(users, n, U, V, J, Jp, Kp, bu, bv, b0, clamp, lo, hi, S1, S2);
     return hipGetLastError();
+}
+
+template <typename T, int EPI>
+static hipError_t watch_accum_epi(const uint32_t* users, uint32_t n, const T* U, const T* V, uint32_t J, uint32_t Kp,
+                                  const double* bu, const double* bv, double b0, int clamp, double lo, double hi,
+                                  double* S1, double* S2, hipStream_t st) {
+    if (n == 0 || J == 0) return hipSuccess;
+    // users per workgroup: as many as 64 KB of LDS hold (watch_mu, recommend.h)
+    switch (watch_mu(Kp)) {
+        case 4:
+            return watch_accum_mu<T, 4, EPI>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
+        case 2:
+            return watch_accum_mu<T, 2, EPI>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
+    }
+    return watch_accum_mu<T, 1, EPI>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
 }
 
 template <typename T>
 hipError_t launch_watch_accum(const uint32_t* users, uint32_t n, const T* U, const T* V, uint32_t J, uint32_t Kp,
                               const double* bu, const double* bv, double b0, int clamp, double lo, double hi,
                               double* S1, double* S2, hipStream_t st) {
-    if (n == 0 || J == 0) return hipSuccess;
-    // users per workgroup: as many as 64 KB of LDS hold (Kp <= 112: 64, <= 240: 32, else 16)
-    if (Kp <= 112) return watch_accum_mu<T, 4>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
-    if (Kp <= 240) return watch_accum_mu<T, 2>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
-    return watch_accum_mu<T, 1>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
+    return watch_accum_epi<T, 0>(users, n, U, V, J, Kp, bu, bv, b0, clamp, lo, hi, S1, S2, st);
 }
 template hipError_t launch_watch_accum<double>(const uint32_t*, uint32_t, const double*, const double*, uint32_t,
                                                uint32_t, const double*, const double*, double, int, double, double,
@@ -140,6 +165,24 @@ template hipError_t launch_watch_accum<double>(const uint32_t*, uint32_t, const 
 template hipError_t launch_watch_accum<float>(const uint32_t*, uint32_t, const float*, const float*, uint32_t, uint32_t,
                                               const double*, const double*, double, int, double, double, double*,
                                               double*, hipStream_t);
+
+hipError_t launch_watch_accum_epi(int epi, const uint32_t* rows, uint32_t n, const double* A, const double* B,
+                                  uint32_t J, uint32_t Kp, const double* ba, const double* bb, double b0, int clamp,
+                                  double lo, double hi, double* S1, double* S2, hipStream_t st) {
+    if (!ba || !bb) return hipErrorInvalidValue;
+    switch (epi) {
+        case 0:
+            return watch_accum_epi<double, 0>(rows, n, A, B, J, Kp, ba, bb, b0, clamp, lo, hi, S1, S2, st);
+        case WATCH_EPI_CDF:
+            return watch_accum_epi<double, WATCH_EPI_CDF>(rows, n, A, B, J, Kp, ba, bb, b0, clamp, lo, hi, S1, S2, st);
+        case WATCH_EPI_SET:
+            return watch_accum_epi<double, WATCH_EPI_SET>(rows, n, A, B, J, Kp, ba, bb, b0, clamp, lo, hi, S1, S2, st);
+        case WATCH_EPI_CDF | WATCH_EPI_SET:
+            return watch_accum_epi<double, WATCH_EPI_CDF | WATCH_EPI_SET>(rows, n, A, B, J, Kp, ba, bb, b0, clamp, lo, hi, S1,
+                                                                         S2, st);
+    }
+    return hipErrorInvalidValue;
+}
 
 // ------------------------------------------------------------------ moments and keys
 // One place for the expressions, without contraction: sbmf_watch_scores returns exactly the

@@ -46,7 +46,8 @@ sbmf_ctx::~sbmf_ctx() {
     for (hipEvent_t& e : oev) event_destroy(e);
     for (hipEvent_t& e : wev) event_destroy(e);
     for (hipEvent_t& e : fev) event_destroy(e);
-    for (ScoreList* l : {&watch, &guests}) l->drop();
+    for (ScoreList* l : {&watch, &guests, &fmq}) l->drop();
+    fmqd.drop();
     pinned_free(h_fhyp, h_fhyp_bytes);
     event_destroy(hev);
     stream_destroy(sto);

@@ -18,7 +18,9 @@
 // Beyond libFM: -recommend / -rec_users / -rec_topn / -rec_risk write the SBPMF sampler's
 // posterior top-N items for a list of users (sbmf_watch_users / sbmf_recommend);
 // -rec_guests / -recommend_guests do the same for users outside the training set, given by
-// their ratings (sbmf_foldin_users / sbmf_foldin_recommend).
+// their ratings (sbmf_foldin_users / sbmf_foldin_recommend).  -recommend_queries / -rec_queries /
+// -rec_relation / -rec_exclude write, for libFM's MCMC / ALS learner with -relation, the posterior
+// top-N block rows of one relation for a list of query cases (sbmf_fm_query_cases).
 // Differences, by design: -seed is honoured (libfm.cpp:124 ignores it); on
 // error the exit code is 1 (the reference prints "ERROR" and returns 0).
 #include <algorithm>
@@ -474,6 +476,18 @@ int main(int argc, char** argv) {
         cl.reg("recommend_guests", "filename for output: -recommend's lines for the guests of -rec_guests ('guest<TAB>"
                                    "item<TAB>mean<TAB>stdev', the guest's own items left out); shares -rec_topn and "
                                    "-rec_risk; the SBPMF sampler with the unbiased quirk sets only");
+        // the libFM learner's query list (sbmf_fm_query_cases / sbmf_fm_query_recommend)
+        cl.reg("recommend_queries", "filename for output: per query of -rec_queries the -rec_topn block rows of the "
+                                    "relation -rec_relation with the largest posterior mean prediction (less -rec_risk "
+                                    "stdevs), one 'query<TAB>row<TAB>mean<TAB>stdev' line each; -method mcmc (libFM order) "
+                                    "or als with -relation only");
+        cl.reg("rec_queries", "filename with the queries' main-table features in libFM text format (the target column is "
+                              "ignored); for every relation but -rec_relation's, <stem>.queries holds the block row of "
+                              "each query, one per line [MANDATORY with -recommend_queries]");
+        cl.reg("rec_relation", "the relation whose block rows are ranked: one of -relation's stems [MANDATORY with "
+                               "-recommend_queries]");
+        cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
+                              "numbers non-decreasing");
         if (cl.has("help") || argc == 1) {
             cl.print_help();
             return leave(0);
@@ -503,12 +517,38 @@ int main(int argc, char** argv) {
             throw std::runtime_error("-recommend_guests needs -rec_guests <file> ('guest item rating' per line)");
         if (!recg && cl.has("rec_guests")) throw std::runtime_error("-rec_guests goes with -recommend_guests <file>");
         if (!rec && cl.has("rec_users")) throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
-        if (!rec && !recg && (cl.has("rec_topn") || cl.has("rec_risk")))
+        const bool recq = cl.has("recommend_queries");
+        const char* recq_refusal = "-recommend_queries is offered by libFM's MCMC / ALS learner (-method mcmc -order libfm, "
+                                   "-method als) with -relation: it ranks the block rows of one relation";
+        if (recq && cl.get("recommend_queries", "").empty()) throw std::runtime_error("-recommend_queries needs a file name");
+        if (!recq && (cl.has("rec_queries") || cl.has("rec_relation") || cl.has("rec_exclude")))
+            throw std::runtime_error("-rec_queries / -rec_relation / -rec_exclude go with -recommend_queries <file>");
+        if (recq && cl.get("rec_queries", "").empty())
+            throw std::runtime_error("-recommend_queries needs -rec_queries <file> (the queries in libFM text format)");
+        if (recq && cl.get("rec_relation", "").empty())
+            throw std::runtime_error("-recommend_queries needs -rec_relation <stem> (one of -relation's stems)");
+        if (recq && vb) throw std::runtime_error(recq_refusal);  // before any file is opened
+        std::vector<std::string> rel_stems;
+        {
+            std::stringstream ss(cl.get("relation", ""));
+            std::string stem;
+            while (std::getline(ss, stem, ','))
+                if (!stem.empty()) rel_stems.push_back(stem);
+        }
+        size_t rec_rel = 0;
+        if (recq) {
+            if (rel_stems.empty()) throw std::runtime_error(recq_refusal);
+            rec_rel = std::find(rel_stems.begin(), rel_stems.end(), cl.get("rec_relation", "")) - rel_stems.begin();
+            if (rec_rel == rel_stems.size())
+                throw std::runtime_error("-rec_relation " + cl.get("rec_relation", "") + " names none of -relation's stems (" +
+                                         cl.get("relation", "") + ")");
+        }
+        if (!rec && !recg && !recq && (cl.has("rec_topn") || cl.has("rec_risk")))
             throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
         if (rec && method != "mcmc") throw std::runtime_error(rec_refusal);  // before any file is opened
         if (recg && method != "mcmc") throw std::runtime_error(recg_refusal);
         const long rec_topn = cl.getl("rec_topn", 10);
-        if ((rec || recg) && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
+        if ((rec || recg || recq) && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
         const std::string fmt = cl.get("format", "auto");
         if (fmt != "auto" && fmt != "triple" && fmt != "libfm" && fmt != "binary")
             throw std::runtime_error("unknown -format " + fmt);
@@ -535,6 +575,7 @@ int main(int argc, char** argv) {
                                      (vb ? "-method vb (online VB)" : "-method mcmc -order sbpmf (the SBPMF sampler)") +
                                      " does not read them, and without them the relations' features would be missing");
         if (rec && lfm) throw std::runtime_error(rec_refusal);
+        if (recq && !lfm) throw std::runtime_error(recq_refusal);
         if (recg && (lfm || biased)) throw std::runtime_error(recg_refusal);  // (a guest bias would need its own draw)
         if (method != "mcmc" && !vb && !als)
             throw std::runtime_error("-method " + method + " is not supported (use mcmc, als or vb)");
@@ -737,6 +778,56 @@ int main(int argc, char** argv) {
             if (g_ptr.size() < 2) throw std::runtime_error("-rec_guests: " + gf + " lists no guest");
         }
 
+        // the queries: their main features, a block row of every relation but the candidates', the exclusions
+        sbmf_cases qcases{};
+        std::vector<std::vector<uint32_t>> q_rows(rel_stems.size());
+        std::vector<uint32_t> q_eptr, q_erows;
+        if (recq) {
+            if (sbmf_load_libfm_cases(cl.get("rec_queries", "").c_str(), &qcases) != SBMF_OK)
+                throw std::runtime_error(std::string("-rec_queries: ") + sbmf_loader_error());
+            if (qcases.n == 0) throw std::runtime_error("-rec_queries: " + cl.get("rec_queries", "") + " lists no query");
+            for (size_t r = 0; r < rel_stems.size(); ++r) {
+                if (r == rec_rel) continue;
+                const std::string qf = rel_stems[r] + ".queries";
+                std::ifstream f(qf);
+                if (!f.is_open()) throw std::runtime_error("Unable to open file " + qf);
+                std::string line;
+                while (std::getline(f, line)) {
+                    const size_t p = line.find_first_not_of(" \t\r");
+                    if (p == std::string::npos || line[p] == '#') continue;
+                    char* end = nullptr;
+                    const unsigned long long v = std::strtoull(line.c_str() + p, &end, 10);
+                    if (end == line.c_str() + p || v > 0xfffffffeull)
+                        throw std::runtime_error(qf + ": cannot read a block row from '" + line + "'");
+                    q_rows[r].push_back((uint32_t)v);
+                }
+                if (q_rows[r].size() != qcases.n)
+                    throw std::runtime_error(qf + " holds " + std::to_string(q_rows[r].size()) + " block rows; -rec_queries " +
+                                             std::to_string(qcases.n) + " queries");
+            }
+            if (cl.has("rec_exclude") && !cl.get("rec_exclude", "").empty()) {
+                const std::string ef = cl.get("rec_exclude", "");
+                std::ifstream f(ef);
+                if (!f.is_open()) throw std::runtime_error("Unable to open file " + ef);
+                std::string line;
+                q_eptr.push_back(0);
+                while (std::getline(f, line)) {
+                    const size_t p = line.find_first_not_of(" \t\r");
+                    if (p == std::string::npos || line[p] == '#') continue;
+                    unsigned long long qn = 0, row = 0;
+                    if (std::sscanf(line.c_str() + p, "%llu %llu", &qn, &row) != 2 || row > 0xfffffffeull)
+                        throw std::runtime_error("-rec_exclude: cannot read 'query row' from '" + line + "'");
+                    if (qn >= qcases.n) throw std::runtime_error("-rec_exclude: query number out of range in '" + line + "'");
+                    if (qn + 2 < q_eptr.size())
+                        throw std::runtime_error("-rec_exclude: query numbers must not decrease ('" + line + "')");
+                    while (q_eptr.size() < qn + 2) q_eptr.push_back((uint32_t)q_erows.size());
+                    q_erows.push_back((uint32_t)row);
+                    q_eptr.back() = (uint32_t)q_erows.size();
+                }
+                while (q_eptr.size() < qcases.n + 1) q_eptr.push_back((uint32_t)q_erows.size());
+            }
+        }
+
         sbmf_ctx* ctx = nullptr;
         if (sbmf_create(&cfg, &ctx) != SBMF_OK) throw std::runtime_error(sbmf_last_global_error());
         auto chk = [&](int rc) {
@@ -829,7 +920,29 @@ int main(int argc, char** argv) {
         if (rec) chk(sbmf_watch_users(ctx, (uint32_t)rec_ids.size(), rec_ids.data(), 0));
         if (recg)
             chk(sbmf_foldin_users(ctx, (uint32_t)g_ptr.size() - 1, g_ptr.data(), g_items.data(), g_ratings.data(), 0));
+        if (recq) {
+            std::vector<const uint32_t*> rp(rel_stems.size(), nullptr);
+            for (size_t r = 0; r < rel_stems.size(); ++r)
+                if (r != rec_rel) rp[r] = q_rows[r].data();
+            chk(sbmf_fm_query_cases(ctx, (uint32_t)rec_rel, &qcases, rp.data(), q_erows.empty() ? nullptr : q_eptr.data(),
+                                    q_erows.empty() ? nullptr : q_erows.data(), 0));
+        }
         chk(sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
+        if (recq) {
+            const size_t nq = qcases.n, topn = (size_t)rec_topn, slots = nq * topn;
+            std::vector<uint32_t> it(slots);
+            std::vector<double> mean(slots), sd(slots);
+            chk(sbmf_fm_query_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
+            FILE* f = std::fopen(cl.get("recommend_queries", "").c_str(), "w");
+            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend_queries", ""));
+            for (size_t g = 0; g < nq; ++g)
+                for (size_t k = 0; k < topn; ++k) {
+                    const size_t x = g * topn + k;
+                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
+                    std::fprintf(f, "%zu\t%u\t%.17g\t%.17g\n", g, it[x], mean[x], sd[x]);
+                }
+            std::fclose(f);
+        }
         if (rec) {
             const size_t topn = (size_t)rec_topn, slots = rec_ids.size() * topn;
             std::vector<uint32_t> it(slots);
@@ -876,6 +989,7 @@ int main(int argc, char** argv) {
         sbmf_free_ratings(&te);
         sbmf_free_cases(&ctr);
         sbmf_free_cases(&cte);
+        sbmf_free_cases(&qcases);
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return leave(1);

@@ -710,6 +710,78 @@ class FMLearnSBPMF:
         self._check(lib.sbmf_foldin_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
         return {"ms_draw": a.value, "ms_score": b.value, "ms_select": c.value}
 
+    # -- posterior top-N of query cases over a relation's block rows (libFM's MCMC / ALS learner)
+    def fm_queries(self, relation, cases, rows=None, exclude=None, clamp=False):
+        """Register a query list (sbmf_fm_query_cases): ``relation`` is the index of the relation
+        whose block rows are ranked, ``cases`` the queries' main-table features as Cases (targets
+        ignored), ``rows`` one sequence of block-row indices per relation (the candidates' entry
+        may be None; ``rows`` itself may be None with one relation), ``exclude`` per query the
+        block rows left out of its top-N -- a list of sequences, or a CSR (ptr, rows) of two 1-D
+        numpy arrays.  From the next iteration on every query's score against every block row is
+        accumulated; ``clamp`` clamps each iteration's score like the test prediction.  Cases
+        without a case drop the list and free its device buffers."""
+        if not isinstance(cases, Cases):
+            raise ValueError("fm_queries takes Cases")
+        n = cases.num_cases
+        nrel = len(self._relations)
+        keep = [None] * nrel  # the arrays the pointer table points into
+        arr = (_lib._P_U32 * max(nrel, 1))()
+        for r in range(nrel):
+            if rows is not None and r < len(rows) and rows[r] is not None:
+                keep[r] = _u32(rows[r]).ravel()
+                if len(keep[r]) != n:
+                    raise ValueError("rows[%d] holds %d block rows; %d queries" % (r, len(keep[r]), n))
+                arr[r] = _ptr(keep[r], C.c_uint32)
+        eptr = erows = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in exclude):
+                eptr, erows = _u32(exclude[0]), _u32(exclude[1])
+            else:
+                if len(exclude) != n:
+                    raise ValueError("exclude holds %d lists; %d queries" % (len(exclude), n))
+                eptr = _u32(np.concatenate([[0], np.cumsum([len(e) for e in exclude])]))
+                erows = _u32(np.concatenate([np.asarray(e, dtype=np.int64).ravel() for e in exclude] + [np.zeros(0, np.int64)]))
+            if len(eptr) != n + 1:
+                raise ValueError("the exclusion ptr holds %d values; %d queries" % (len(eptr), n))
+            if len(erows) == 0:
+                erows = np.zeros(1, np.uint32)
+        c = cases._c()
+        self._check(lib.sbmf_fm_query_cases(self.ctx, int(relation), C.byref(c), arr if nrel else None,
+                                            _ptr(eptr, C.c_uint32) if eptr is not None else None,
+                                            _ptr(erows, C.c_uint32) if erows is not None else None, 1 if clamp else 0))
+        self._n_queries = n
+        self._query_rows = self.fm_relation_info()[int(relation)]["block_rows"] if n else 0
+
+    def fm_query_scores(self, q):
+        """(mean, stdev) of query ``q`` over the iterations accumulated since ``fm_queries`` (ALS: the
+        latest iteration, stdev 0), one value per block row of the candidates' relation."""
+        nb = getattr(self, "_query_rows", 0)
+        mean, sd = np.zeros(max(nb, 1)), np.zeros(max(nb, 1))
+        self._check(lib.sbmf_fm_query_scores(self.ctx, int(q), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        return mean[:nb], sd[:nb]
+
+    def fm_query_recommend(self, topn=10, risk=0.0, keep_excluded=False):
+        """Per query the ``topn`` block rows with the largest mean - risk * stdev (ties by ascending
+        row), without the query's excluded rows unless ``keep_excluded``.  Returns (rows int64
+        [n, topn] with -1 in empty slots, mean, stdev); empty slots hold NaN."""
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        n, t = getattr(self, "_n_queries", 0), int(topn)
+        rows = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(rows.shape, np.nan), np.full(rows.shape, np.nan)
+        self._check(lib.sbmf_fm_query_recommend(self.ctx, t, 1 if keep_excluded else 0, float(risk),
+                                                _ptr(rows, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = rows[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def fm_query_timing(self):
+        """Device ms of the last iteration's query terms and operand copy, of its scoring launch,
+        and of the last selection."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(lib.sbmf_fm_query_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"ms_terms": a.value, "ms_score": b.value, "ms_select": c.value}
+
     def close(self):
         if self.ctx is not None:
             lib.sbmf_destroy(self.ctx)

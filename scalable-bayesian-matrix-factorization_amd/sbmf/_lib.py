@@ -119,6 +119,11 @@ SIGNATURES = {
     "sbmf_foldin_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
     "sbmf_foldin_recommend": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
     "sbmf_foldin_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
+    "sbmf_fm_query_cases": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CasesC), C.POINTER(_P_U32), _P_U32, _P_U32,
+                                      C.c_uint32]),
+    "sbmf_fm_query_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_fm_query_recommend": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
+    "sbmf_fm_query_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
     "sbmf_comm_unique_id": (C.c_int, [_P_U8]),
     "sbmf_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P_U8]),
     "sbmf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _P_U8, C.POINTER(C.c_void_p)]),
@@ -163,6 +168,7 @@ SIGNATURES = {
     "sbmf_test_stage_ms": (C.c_int, [C.c_void_p, _P_F64, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sbmf_test_rccl_selftest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(RcclSelftest)]),
     "sbmf_test_device_usage": (C.c_int, [C.c_int, C.POINTER(DeviceUsage)]),
+    "sbmf_test_watch_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
 }
 
 
