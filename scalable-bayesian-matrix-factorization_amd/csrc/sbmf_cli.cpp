@@ -7,14 +7,14 @@
 // flags are libFM's (libfm.cpp:86-111) plus the sampler's own settings.
 // Output follows fm_learn_mcmc_simultaneous.h: per sweep
 //   "#Iter=%3d\tTrain=<rmse>\tTest=<rmse>"                      (:244)
+// and the file test_rmse_<k0><k1><K>_<method> (truncated at start, one
+// running-mean test RMSE per line, :57-62,146); -out writes one averaged
+// prediction per test line (libfm.cpp:629-634).
 // -method mcmc (libFM order) and -method als read libFM text with any number of features per
 // case (sbmf_load_libfm_cases -> the general learner, fmg.cpp); a file of "user:1 item:1"
 // cases takes the two-attribute learner.  -meta FILE (one attribute group id per attribute)
 // gives those two methods libFM's per-group hyperparameters (sbmf_set_attr_groups; -regular then
 // also takes 1 + 2G values); a two-feature file with -meta takes the general learner.
-// and the file test_rmse_<k0><k1><K>_<method> (truncated at start, one
-// running-mean test RMSE per line, :57-62,146); -out writes one averaged
-// prediction per test line (libfm.cpp:629-634).
 // Beyond libFM: -recommend / -rec_users / -rec_topn / -rec_risk write the SBPMF sampler's
 // posterior top-N items for a list of users (sbmf_watch_users / sbmf_recommend);
 // -rec_guests / -recommend_guests do the same for users outside the training set, given by
@@ -55,20 +55,10 @@ struct CmdLine {
     }
     CmdLine(int argc, char** argv) {
         for (int i = 1; i < argc; ++i) {
-            std::string s(argv[i]);
+            std::string s(argv[i]), nx(i + 1 < argc ? argv[i + 1] : "-");
             if (!parse_name(s)) throw std::runtime_error("cannot parse " + s);
             if (value.count(s)) throw std::runtime_error("the parameter " + s + " is already specified");
-            if (i + 1 < argc) {
-                std::string nx(argv[i + 1]);
-                if (!parse_name(nx)) {
-                    value[s] = argv[i + 1];
-                    ++i;
-                } else {
-                    value[s] = "";
-                }
-            } else {
-                value[s] = "";
-            }
+            value[s] = parse_name(nx) ? "" : argv[++i];  // followed by another flag, or by nothing: the empty value
         }
     }
     void reg(const std::string& n, const std::string& h) { help[n] = h; }
@@ -91,47 +81,84 @@ struct CmdLine {
 
 // cmdline.h getStrValues: comma / semicolon separated tokens
 std::vector<std::string> split_strs(const std::string& s) {
-    std::vector<std::string> out;
-    std::string cur;
-    for (char ch : s) {
-        if (ch == ',' || ch == ';') {
-            out.push_back(cur);
-            cur.clear();
-        } else {
-            cur += ch;
-        }
-    }
-    if (!cur.empty()) out.push_back(cur);
+    std::vector<std::string> out(1);
+    for (char ch : s)
+        if (ch == ',' || ch == ';') out.emplace_back();
+        else out.back() += ch;
+    if (out.back().empty()) out.pop_back();  // nothing after the last separator is no token
     return out;
 }
 
 std::vector<int> split_ints(const std::string& s) {
     std::vector<int> out;
-    std::string cur;
-    for (char ch : s) {
-        if (ch == ',' || ch == ';') {
-            out.push_back(std::atoi(cur.c_str()));
-            cur.clear();
-        } else {
-            cur += ch;
-        }
-    }
-    if (!cur.empty()) out.push_back(std::atoi(cur.c_str()));
+    for (const std::string& x : split_strs(s)) out.push_back(std::atoi(x.c_str()));
     return out;
 }
 
-bool looks_libfm(const std::string& path) {
+[[noreturn]] void fail(const std::string& message) { throw std::runtime_error(message); }
+bool exists(const std::string& f) { return std::ifstream(f).good(); }
+
+// The line grammar of the train file's first look and of every list file: blank lines and lines whose
+// first non-blank character is '#' are skipped; fn(line, s) gets each other line whole (the messages
+// quote it) and from its first non-blank character, and returns whether to read on.
+template <class Fn>
+void read_lines(const std::string& path, Fn fn) {
     std::ifstream f(path);
+    if (!f.is_open()) fail("Unable to open file " + path);
     std::string line;
     while (std::getline(f, line)) {
-        size_t p = line.find_first_not_of(" \t\r");
+        const size_t p = line.find_first_not_of(" \t\r");
         if (p == std::string::npos || line[p] == '#') continue;
-        return line.find(':') != std::string::npos;
+        if (!fn(line, line.c_str() + p)) return;
     }
-    return false;
 }
 
-bool exists(const std::string& f) { return std::ifstream(f).good(); }
+// the first such line holds a "feature:value" (a file that cannot be opened does not: the loader reports it)
+bool looks_libfm(const std::string& path) {
+    bool colon = false;
+    if (exists(path))
+        read_lines(path, [&](const std::string& line, const char*) {
+            colon = line.find(':') != std::string::npos;
+            return false;
+        });
+    return colon;
+}
+
+// One id per line (-rec_users, <stem>.queries); the message names the list (`where`) and what a line holds (`what`)
+std::vector<uint32_t> read_ids(const std::string& path, const std::string& where, const char* what) {
+    std::vector<uint32_t> ids;
+    read_lines(path, [&](const std::string& line, const char* s) {
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(s, &end, 10);
+        if (end == s || v > 0xfffffffeull) fail(where + ": cannot read a " + what + " from '" + line + "'");
+        ids.push_back((uint32_t)v);
+        return true;
+    });
+    return ids;
+}
+
+// "number fields.." per line, the numbers non-decreasing (-rec_guests, -rec_exclude), as a CSR over the numbers: a
+// skipped number is a group without values.  parse(s, line, number) reads a line and says whether it could (it may refuse
+// the number itself); value(line) then checks and returns what the line adds.  `flag`, `fields`, `noun`: the messages' words.
+struct Grouped { std::vector<uint32_t> ptr, val; };
+template <class Parse, class Value>
+Grouped read_grouped(const std::string& path, const std::string& flag, const char* fields, const char* noun, Parse parse,
+                     Value value) {
+    Grouped c;
+    c.ptr.push_back(0);
+    read_lines(path, [&](const std::string& line, const char* s) {
+        unsigned long long g = 0;
+        if (!parse(s, line, g)) fail(flag + ": cannot read '" + fields + "' from '" + line + "'");
+        if (g + 2 < c.ptr.size())  // the open group is number ptr.size() - 2
+            fail(flag + ": " + noun + " numbers must not decrease ('" + line + "')");
+        const uint32_t v = value(line);
+        while (c.ptr.size() < g + 2) c.ptr.push_back((uint32_t)c.val.size());  // opens group g (and skipped ones)
+        c.val.push_back(v);
+        c.ptr.back() = (uint32_t)c.val.size();
+        return true;
+    });
+    return c;
+}
 
 // Data::load (Data.h:112-117) takes <stem>.data/.datat/.target or <stem>.x/.xt/.y,
 // each orientation only when the data set needs it, before the text file itself.
@@ -150,14 +177,9 @@ bool rowmajor_only(const std::string& stem) {
 
 void load(const std::string& path, const std::string& fmt, uint32_t item_offset, bool has_x, sbmf_ratings& r) {
     int rc;
-    if (fmt == "binary" || (fmt == "auto" && has_binary(path, has_x))) {
-        if (has_binary(path, has_x)) {
-            rc = sbmf_load_libfm_data(path.c_str(), has_x, 1, item_offset, &r);
-        } else if (rowmajor_only(path) || fmt == "binary") {
-            rc = sbmf_load_libfm_binary(path.c_str(), item_offset, &r);
-        } else {
-            rc = sbmf_load_libfm(path.c_str(), item_offset, &r);
-        }
+    if (fmt == "binary" || (fmt == "auto" && has_binary(path, has_x))) {  // -format binary without the set: the pair
+        rc = has_binary(path, has_x) ? sbmf_load_libfm_data(path.c_str(), has_x, 1, item_offset, &r)
+                                     : sbmf_load_libfm_binary(path.c_str(), item_offset, &r);
     } else if (fmt == "auto" && rowmajor_only(path)) {
         std::cerr << "note: " << path << ": no " << (has_x ? "" : "transpose (.xt/.datat) or ")
                   << "text file of that name (bin/libFM would stop here); reading the row-major binary pair"
@@ -176,14 +198,10 @@ void load(const std::string& path, const std::string& fmt, uint32_t item_offset,
 // a file whose item ids do not all lie above every user id has no users-first
 // reading and is refused.
 uint32_t users_first_offset(sbmf_ratings& tr, sbmf_ratings& te) {
+    if (tr.n + te.n == 0) return 0;
     uint64_t umax = 0;
-    bool any = false;
     for (const sbmf_ratings* r : {&tr, &te})
-        for (uint64_t q = 0; q < r->n; ++q) {
-            umax = std::max<uint64_t>(umax, r->user[q]);
-            any = true;
-        }
-    if (!any) return 0;
+        for (uint64_t q = 0; q < r->n; ++q) umax = std::max<uint64_t>(umax, r->user[q]);
     const uint32_t I = (uint32_t)(umax + 1);
     for (sbmf_ratings* r : {&tr, &te})
         for (uint64_t q = 0; q < r->n; ++q)
@@ -339,14 +357,10 @@ void rlog_line(const sbmf_sweep_info* in, RunState& rs) {
 int on_sweep(const sbmf_sweep_info* in, void* user) {
     RunState* rs = static_cast<RunState*>(user);
     if (in->collected) rs->ncol++;
-    const double test = rs->cls ? in->acc_avg : in->rmse_avg;
-    if (rs->vb)
-        std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTest=" << in->rmse_avg << std::endl;
-    else if (rs->cls)  // fm_learn_mcmc_simultaneous.h:275 without its MAP@5 field
-        std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTrain=" << in->acc_train << "\tTest=" << test << std::endl;
-    else
-        std::cout << "#Iter=" << std::setw(3) << in->sweep << "\tTrain=" << in->rmse_train << "\tTest=" << in->rmse_avg
-                  << std::endl;
+    // online VB has no Train field; -task c prints accuracies (fm_learn_mcmc_simultaneous.h:275 without its MAP@5 field)
+    std::cout << "#Iter=" << std::setw(3) << in->sweep;
+    if (!rs->vb) std::cout << "\tTrain=" << (rs->cls ? in->acc_train : in->rmse_train);
+    std::cout << "\tTest=" << (rs->cls ? in->acc_avg : in->rmse_avg) << std::endl;
     std::ofstream f(rs->rmse_file, std::ios_base::app);
     if (!rs->cls) f << in->rmse_avg << "\n";  // libFM writes the file's lines in regression only (:245)
     if (rs->rlog) rlog_line(in, *rs);
@@ -355,12 +369,6 @@ int on_sweep(const sbmf_sweep_info* in, void* user) {
     return 0;
 }
 
-// SBMF_EXIT=guard (opt-in; round 3's default): leave through sbmf_exit_guard's
-// handler (registered at main's start, before the first HIP call), so a profiler's
-// exit handlers still run and the shared-library finalizers do not.  The finalizer
-// fault it skipped under rocprofv3 came with RCCL linked at load time; libsbmf
-// dlopens RCCL only for a multi-GPU communicator now, and the CLI exits normally
-// under rocprofv3 (profiles/r04/r04s2_cli_rocprof_kernel_stats.csv, DESIGN.md §10).
 // -regular for libFM's learners (libfm.cpp:484-521): none, one value for all, 'r0,r1,r2', or with
 // G -meta groups 'r0, w_lambda[0..G-1], v_lambda[0..G-1]' (1 + 2G values; for G = 1 the two
 // readings of three values coincide).  gw / gv stay empty unless the per-group form was given.
@@ -392,6 +400,561 @@ void parse_regular(const std::string& text, uint32_t G, double& r0, double& rw, 
     }
 }
 
+void register_flags(CmdLine& cl) {
+    // libFM's flags (libfm.cpp:86-111)
+    cl.reg("task", "r=regression, c=binary classification (libFM's probit model: targets <= 0 are the negative "
+                   "class; -method als and -method mcmc in libFM order only) [MANDATORY]");
+    cl.reg("meta", "filename with one attribute group id per attribute (libFM's -meta): -method mcmc (libFM order) "
+                   "and -method als draw their hyperparameters per group, and a two-feature input then takes the "
+                   "general learner; ignored by the SBPMF sampler (-order sbpmf: one user and one item group) and "
+                   "by -method vb");
+    cl.reg("train", "filename for training data [MANDATORY] (SBPMF triples or libFM text)");
+    cl.reg("test", "filename for test data [MANDATORY]");
+    cl.reg("validation", "unused (SGDA only in libFM)");
+    cl.reg("out", "filename for output: averaged test predictions");
+    cl.reg("dim", "'k0,k1,k2': k0=use bias, k1=use 1-way interactions, k2=dim of 2-way interactions; default=1,1,8");
+    cl.reg("regular", "'r0,r1,r2' (or one value for all) for -method als and -method mcmc -order libfm: "
+                      "fixed / starting precisions of w0, w, v (libfm.cpp:484-513); with the G groups of -meta also "
+                      "'r0,w[0],..,w[G-1],v[0],..,v[G-1]' (1 + 2G values, :514-521); default=0");
+    cl.reg("init_stdev", "stdev for initialization of the factors; default: 1.0 (quirks final) / 0.1 (sbpmf2)");
+    cl.reg("stdev", "unused");
+    cl.reg("iter", "number of collection sweeps; default=100");
+    cl.reg("learn_rate", "unused (SGD only)");
+    cl.reg("method", "learning method: mcmc (SBPMF Gibbs; with -order libfm libFM's own MCMC chain) | "
+                     "als (libFM's ALS) | vb (online variational Bayes, libFM's vb_online; alias vb_online); "
+                     "default=mcmc");
+    cl.reg("order", "-method mcmc: libfm (libFM's fm_learn_mcmc chain: f-outer, one hyperprior group, w0 / w "
+                    "per -dim k0,k1, sqrt(variance) stdev; default on libFM text / binary input, as bin/libFM) | "
+                    "sbpmf (the SBPMF sampler of gibbs_sbpmf_final.cpp; default on SBPMF triple input)");
+    cl.reg("verbosity", "how much infos to print; default=0");
+    cl.reg("rlog", "write per-sweep measurements to a TSV file; default=''");
+    cl.reg("seed", "integer seed; default=1 (glibc default seed of the reference samplers)");
+    cl.reg("help", "this screen");
+    cl.reg("relation", "BS: comma-separated stems of block-structure relations (libFM's -relation: <stem>.xt or .x, "
+                       "<stem>.train, <stem>.test, optional <stem>.groups): -method mcmc (libFM order) and -method als");
+    cl.reg("cache_size", "unused (binary data format)");
+    // sampler settings
+    cl.reg("rng", "ref (reference glibc/Leva/Marsaglia-Tsang stream; default) | philox (in-kernel, throughput)");
+    cl.reg("quirks", "final (gibbs_sbpmf_final.cpp; default) | sbpmf2 | none (stdev = sqrt(variance)) | bias2 | bias22 "
+                     "(biased sampler, top-level gibbs_sbpmf2.cpp / gibbs_sbpmf22.cpp; needs -dim '1,1,K')");
+    cl.reg("precision", "f64 (default) | f32");
+    cl.reg("burnin", "burn-in sweeps before collection; default=0");
+    cl.reg("average", "running-mean divisor: default (quirk set) | collected (collected sweeps only) | "
+                      "reference (sweep + 1, counts burn-in as gibbs_sbpmf_final.cpp:559 does)");
+    cl.reg("format", "auto (default: libFM's binary files if present -- <name>.xt/.y or .datat/.target for "
+                      "-method mcmc|als, <name>.x/.xt/.y or .data/.datat/.target for vb (Data.h:112-117) --, else "
+                      "triple or libfm text) | triple | libfm | binary");
+    cl.reg("item_offset", "libFM input: item feature id offset; default: libFM's num_user (max user feature "
+                          "id + 1, libfm.cpp:375) for -method mcmc (libFM order) / als / vb, 0 for -order sbpmf");
+    cl.reg("device", "HIP device ordinal; default=0");
+    cl.reg("recompute_every", "recompute residuals from scratch every n sweeps; default=1");
+    cl.reg("stream_threshold", "rows with more ratings take the streaming kernel; default=256 (f64) / 512 (f32)");
+    cl.reg("split_chunk", "streaming task size; longer rows are split into chunks on several workgroups; default: "
+                          "the register capacity of the workgroup shape (512 / 1024 / 2048 f64 ratings for 4 / 8 / "
+                          "16 waves), larger values are capped to it");
+    // posterior top-N for a list of users (sbmf_watch_users / sbmf_recommend)
+    cl.reg("recommend", "filename for output: per user of -rec_users the -rec_topn unrated items with the largest "
+                        "posterior mean score (less -rec_risk stdevs), one 'user<TAB>item<TAB>mean<TAB>stdev' line "
+                        "each, ids as in the input files; the SBPMF sampler only (-method mcmc -order sbpmf); on "
+                        "libFM input the item offset then defaults to libFM's num_user");
+    cl.reg("rec_users", "filename with one user id per line [MANDATORY with -recommend]");
+    cl.reg("rec_topn", "items per user, 1..1024; default=10");
+    cl.reg("rec_risk", "rank by mean - x * stdev (a lower confidence bound for x > 0); default=0");
+    // the same for guests: users outside the training set (sbmf_foldin_users / sbmf_foldin_recommend)
+    cl.reg("rec_guests", "filename with one 'guest item rating' line per rating of a user outside the training "
+                         "set: guests numbered from 0, the numbers non-decreasing (a skipped number is a guest "
+                         "without ratings), item ids as -recommend prints them [MANDATORY with -recommend_guests]");
+    cl.reg("recommend_guests", "filename for output: -recommend's lines for the guests of -rec_guests ('guest<TAB>"
+                               "item<TAB>mean<TAB>stdev', the guest's own items left out); shares -rec_topn and "
+                               "-rec_risk; the SBPMF sampler with the unbiased quirk sets only");
+    // the libFM learner's query list (sbmf_fm_query_cases / sbmf_fm_query_recommend)
+    cl.reg("recommend_queries", "filename for output: per query of -rec_queries the -rec_topn block rows of the "
+                                "relation -rec_relation with the largest posterior mean prediction (less -rec_risk "
+                                "stdevs), one 'query<TAB>row<TAB>mean<TAB>stdev' line each; -method mcmc (libFM order) "
+                                "or als with -relation only");
+    cl.reg("rec_queries", "filename with the queries' main-table features in libFM text format (the target column is "
+                          "ignored); for every relation but -rec_relation's, <stem>.queries holds the block row of "
+                          "each query, one per line [MANDATORY with -recommend_queries]");
+    cl.reg("rec_relation", "the relation whose block rows are ranked: one of -relation's stems [MANDATORY with "
+                           "-recommend_queries]");
+    cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
+                          "numbers non-decreasing");
+}
+
+// The command line, resolved once (resolve).  A ListOpt is one of the three top-N lists: its output flag is given
+// (-recommend, -recommend_guests, -recommend_queries), the list's input (-rec_users, -rec_guests, -rec_queries), the output.
+struct ListOpt { bool on = false; std::string in, out; };
+struct Options {
+    bool cls = false;  // -task c
+    std::string method, fmt, train, test, relation, meta, regular, rlog, out, exclude;
+    // the learner selected: online VB | libFM's fm_learn_mcmc chain (ALS is one) | the SBPMF sampler, biased or not
+    bool vb = false, als = false, lfm = false, biased = false;
+    bool has_x = false, libfm_input = false;  // what the train file is read as (has_x: Data::load's row-major set)
+    std::vector<int> dim;
+    sbmf_config cfg;
+    ListOpt users, guests, queries;
+    long topn = 10;  // -rec_topn and -rec_risk, shared by the three
+    double risk = 0.0;
+    std::vector<std::string> rel_stems;  // -relation's stems, and which of them -rec_relation names
+    size_t rec_rel = 0;
+    bool has_item_offset = false;
+    uint32_t item_offset = 0;
+    int verbosity = 0;
+};
+
+const char* const task_refusal = "only -task r (regression) is supported by the SBPMF sampler";
+const char* const rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
+const char* const recg_refusal = "-recommend_guests is offered by the SBPMF sampler (-method mcmc -order sbpmf) with "
+                                 "the unbiased quirk sets (final, sbpmf2, none)";
+const char* const recq_refusal = "-recommend_queries is offered by libFM's MCMC / ALS learner (-method mcmc -order libfm, "
+                                 "-method als) with -relation: it ranks the block rows of one relation";
+
+// Step 1 of the refusals: what the flags alone decide, before any file is opened.  Read top to bottom, this is
+// the order in which one of several applicable messages wins.
+void resolve_flags(const CmdLine& cl, Options& o) {
+    const std::string task = cl.get("task", "");
+    if (task != "r" && task != "c") fail(task_refusal);
+    o.cls = task == "c";
+    o.method = cl.get("method", "mcmc");
+    o.vb = o.method == "vb" || o.method == "vb_online";
+    // -task c is libFM's MCMC / ALS learner's: every other route is refused before a file is
+    // looked at where the flags alone decide it (-method vb, -order sbpmf, -quirks, triple input)
+    if (o.cls && (o.vb || cl.get("order", "") == "sbpmf" || (cl.has("quirks") && !cl.has("order")) ||
+                  cl.get("format", "auto") == "triple"))
+        fail(task_refusal);
+    ListOpt &rec = o.users, &recg = o.guests, &recq = o.queries;
+    rec = {cl.has("recommend"), cl.get("rec_users", ""), cl.get("recommend", "")};
+    recg = {cl.has("recommend_guests"), cl.get("rec_guests", ""), cl.get("recommend_guests", "")};
+    recq = {cl.has("recommend_queries"), cl.get("rec_queries", ""), cl.get("recommend_queries", "")};
+    if (rec.on && rec.out.empty()) fail("-recommend needs a file name");
+    if (rec.on && rec.in.empty()) fail("-recommend needs -rec_users <file> (one user id per line)");
+    if (recg.on && recg.out.empty()) fail("-recommend_guests needs a file name");
+    if (recg.on && recg.in.empty()) fail("-recommend_guests needs -rec_guests <file> ('guest item rating' per line)");
+    if (!recg.on && cl.has("rec_guests")) fail("-rec_guests goes with -recommend_guests <file>");
+    if (!rec.on && cl.has("rec_users")) fail("-rec_users / -rec_topn / -rec_risk go with -recommend");
+    if (recq.on && recq.out.empty()) fail("-recommend_queries needs a file name");
+    if (!recq.on && (cl.has("rec_queries") || cl.has("rec_relation") || cl.has("rec_exclude")))
+        fail("-rec_queries / -rec_relation / -rec_exclude go with -recommend_queries <file>");
+    if (recq.on && recq.in.empty()) fail("-recommend_queries needs -rec_queries <file> (the queries in libFM text format)");
+    const std::string rec_relation = cl.get("rec_relation", "");
+    if (recq.on && rec_relation.empty()) fail("-recommend_queries needs -rec_relation <stem> (one of -relation's stems)");
+    if (recq.on && o.vb) fail(recq_refusal);  // before any file is opened
+    o.relation = cl.get("relation", "");
+    std::stringstream ss(o.relation);
+    for (std::string stem; std::getline(ss, stem, ',');)
+        if (!stem.empty()) o.rel_stems.push_back(stem);
+    if (recq.on) {
+        if (o.rel_stems.empty()) fail(recq_refusal);
+        o.rec_rel = std::find(o.rel_stems.begin(), o.rel_stems.end(), rec_relation) - o.rel_stems.begin();
+        if (o.rec_rel == o.rel_stems.size())
+            fail("-rec_relation " + rec_relation + " names none of -relation's stems (" + o.relation + ")");
+    }
+    if (!rec.on && !recg.on && !recq.on && (cl.has("rec_topn") || cl.has("rec_risk")))
+        fail("-rec_users / -rec_topn / -rec_risk go with -recommend");
+    if (rec.on && o.method != "mcmc") fail(rec_refusal);  // before any file is opened
+    if (recg.on && o.method != "mcmc") fail(recg_refusal);
+    o.topn = cl.getl("rec_topn", 10);
+    if ((rec.on || recg.on || recq.on) && (o.topn < 1 || o.topn > 1024)) fail("-rec_topn must be in 1..1024");
+    o.risk = cl.getd("rec_risk", 0.0);
+    o.exclude = cl.get("rec_exclude", "");
+    o.fmt = cl.get("format", "auto");
+    if (o.fmt != "auto" && o.fmt != "triple" && o.fmt != "libfm" && o.fmt != "binary") fail("unknown -format " + o.fmt);
+}
+
+// Step 2: what also depends on the kind of input, for which -format auto looks into the train file (the first
+// file read); in this order.  Nothing is loaded yet.
+void resolve_learner(const CmdLine& cl, Options& o) {
+    // bin/libFM -method mcmc runs fm_learn_mcmc on libFM data (libfm.cpp:411-419); the SBPMF
+    // sampler reads the triple files of gibbs_sbpmf_final.cpp:43
+    o.train = cl.get("train", "");
+    o.test = cl.get("test", "");
+    // the MCMC and ALS sets carry no row-major data (libfm.cpp:140-149): they read the transpose
+    o.has_x = o.vb;
+    o.libfm_input = o.fmt == "libfm" || o.fmt == "binary" ||
+                    (o.fmt == "auto" && (has_binary(o.train, o.has_x) || rowmajor_only(o.train) || looks_libfm(o.train)));
+    const std::string order = cl.get("order", o.libfm_input ? "libfm" : "sbpmf");
+    if (order != "sbpmf" && order != "libfm") fail("unknown -order " + order);
+    o.als = o.method == "als";
+    const std::string q = cl.get("quirks", "final");
+    o.biased = q == "bias2" || q == "bias22";
+    // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
+    o.lfm = o.als || (o.method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
+    if (o.cls && !o.lfm) fail(task_refusal);
+    // unlike -meta, -relation cannot be ignored: the relations' features would be missing (before any relation is opened)
+    if (!o.lfm && !o.relation.empty())
+        fail(std::string("-relation: block-structure relations are drawn by libFM's MCMC / ALS learner "
+                         "(-method mcmc -order libfm, -method als); ") +
+             (o.vb ? "-method vb (online VB)" : "-method mcmc -order sbpmf (the SBPMF sampler)") +
+             " does not read them, and without them the relations' features would be missing");
+    if (o.users.on && o.lfm) fail(rec_refusal);
+    if (o.queries.on && !o.lfm) fail(recq_refusal);
+    if (o.guests.on && (o.lfm || o.biased)) fail(recg_refusal);  // (a guest bias would need its own draw)
+    if (o.method != "mcmc" && !o.vb && !o.als) fail("-method " + o.method + " is not supported (use mcmc, als or vb)");
+    if (!cl.has("train") || !cl.has("test")) fail("-train and -test are mandatory");
+    const std::vector<int>& dim = o.dim = split_ints(cl.get("dim", "1,1,8"));
+    if (dim.size() != 3) fail("dim must have 3 numbers");
+    if (dim[2] <= 0 || dim[2] > 256) fail("dim k2 must be in [1,256]");
+    if (o.vb && !(dim[0] == 1 && dim[1] == 1)) fail("the online VB learner updates w0 and the user/item w: use -dim '1,1,K'");
+    if (o.lfm && o.biased) fail("-quirks bias2|bias22 selects the SBPMF biased sampler, not libFM's");
+    if (!o.vb && !o.lfm && !o.biased && (dim[0] || dim[1]))  // stdout stays libFM's
+        std::cerr << "note: -order sbpmf: bias terms (k0,k1) are not sampled; the reference SBPMF sampler has "
+                     "them compiled out (gibbs_sbpmf_final.cpp:276-295); -quirks bias2|bias22 selects the biased "
+                     "sampler, -order libfm libFM's own chain" << std::endl;
+    if (o.biased && !(dim[0] == 1 && dim[1] == 1))
+        fail("the biased sampler (gibbs_sbpmf2.cpp) samples b0 and the user/item biases: use -dim '1,1,K'");
+}
+
+// the refusals, then the sbmf_config of the learner they settled (-regular joins it once the groups are counted: load_data)
+Options resolve(const CmdLine& cl) {
+    Options o;
+    resolve_flags(cl, o);
+    resolve_learner(cl, o);
+    sbmf_config& cfg = o.cfg;
+    sbmf_config_default(&cfg);
+    cfg.num_factor = (uint32_t)o.dim[2];
+    cfg.num_iter = (uint32_t)cl.getl("iter", 100);
+    cfg.burnin = (uint32_t)cl.getl("burnin", 0);
+    const std::string av = cl.get("average", "default");
+    if (av == "default") cfg.average = 0;
+    else if (av == "collected") cfg.average = 1;
+    else if (av == "reference") cfg.average = 2;
+    else fail("unknown -average " + av);
+    cfg.seed = (uint64_t)cl.getl("seed", 1);
+    cfg.rng_mode = cl.get("rng", "ref") == "philox" ? SBMF_RNG_PHILOX : SBMF_RNG_REFERENCE;
+    // on_sweep prints and appends to files, never stops the run and reads no device state: in
+    // Philox mode the next sweep's start is queued before it runs (sbmf_config.pipeline)
+    cfg.pipeline = 1;
+    const std::string q = cl.get("quirks", "final");
+    if (q == "sbpmf2") cfg.quirks = SBMF_QUIRKS_SBPMF2;
+    else if (q == "none") cfg.quirks = SBMF_QUIRKS_NONE;
+    else if (q == "bias2") cfg.quirks = SBMF_QUIRKS_BIAS2;
+    else if (q == "bias22") cfg.quirks = SBMF_QUIRKS_BIAS22;
+    else if (q == "final") cfg.quirks = SBMF_QUIRKS_FINAL;
+    else fail("unknown -quirks " + q);
+    cfg.precision = cl.get("precision", "f64") == "f32" ? SBMF_F32 : SBMF_F64;
+    cfg.device = (int32_t)cl.getl("device", 0);
+    if (cl.has("init_stdev")) cfg.init_stdev = cl.getd("init_stdev", 1.0);
+    cfg.recompute_every = (uint32_t)cl.getl("recompute_every", 1);
+    cfg.stream_threshold = (uint32_t)cl.getl("stream_threshold", 0);
+    cfg.split_chunk = (uint32_t)cl.getl("split_chunk", 0);
+    cfg.eval_train = o.vb ? 0 : 1;
+    cfg.method = o.vb ? SBMF_METHOD_VB : o.als ? SBMF_METHOD_ALS : o.lfm ? SBMF_METHOD_LIBFM_MCMC : SBMF_METHOD_MCMC;
+    cfg.task = o.cls ? SBMF_TASK_CLASSIFICATION : SBMF_TASK_REGRESSION;
+    if (o.lfm) {
+        cfg.libfm_dim = (o.dim[0] ? 1u : 0u) | (o.dim[1] ? 2u : 0u);
+        if (!cl.has("init_stdev")) cfg.init_stdev = 0.1;  // libfm.cpp:127
+    }
+    cfg.eval_test = 1;
+    o.meta = cl.get("meta", "");
+    o.regular = cl.get("regular", "");
+    o.rlog = cl.get("rlog", "");
+    o.out = cl.get("out", "");
+    o.has_item_offset = cl.has("item_offset");
+    o.item_offset = (uint32_t)cl.getl("item_offset", 0);
+    o.verbosity = (int)cl.getl("verbosity", 0);
+    return o;
+}
+
+struct RelFiles {  // -relation (libfm.cpp:301-322): a block table and the maps of the train / test cases
+    sbmf_cases block{};
+    uint32_t *train_row = nullptr, *test_row = nullptr, *group = nullptr;
+    uint64_t n_train = 0, n_test = 0;
+    uint32_t G = 0;
+};
+
+// Everything read from files; it owns what the loaders allocated.
+struct HostData {
+    sbmf_ratings tr{}, te{};  // one user and one item per case ...
+    sbmf_cases ctr{}, cte{};  // ... or (general) cases with any number of features
+    bool general = false;
+    bool te_owns_rating = true;  // general input: te.n / te.rating give the -rlog evaluation the targets out of te_y
+    std::vector<double> te_y;
+    uint32_t off = 0;   // the item offset of libFM input, given or inferred
+    uint64_t ioff = 0;  // what the item ids of the list files and the top-N files are moved by: off on libFM input
+    bool grouped = false;  // -meta: a group id per attribute and their number
+    std::vector<uint32_t> meta;
+    uint32_t ngroups = 1;  // the joined groups: the main table's, then every relation's
+    std::vector<double> greg_w, greg_v;
+    std::vector<RelFiles> rels;
+    std::vector<uint32_t> rec_ids;  // -rec_users
+    Grouped guests;                 // -rec_guests as a CSR of items, item ids as the sampler's, and their ratings
+    std::vector<double> g_ratings;
+    // the queries: their main features, a block row of every relation but the candidates', the exclusions
+    sbmf_cases qcases{};
+    std::vector<std::vector<uint32_t>> q_rows;
+    Grouped excl;
+    bool joined() const { return grouped || !rels.empty(); }  // several groups: through the general learner
+    HostData() = default; HostData(const HostData&) = delete;
+    ~HostData() {
+        sbmf_free_ratings(&tr);
+        if (te_owns_rating) sbmf_free_ratings(&te);
+        for (sbmf_cases* c : {&ctr, &cte, &qcases}) sbmf_free_cases(c);
+        for (RelFiles& r : rels) sbmf_free_relation(&r.block, &r.train_row, &r.test_row, &r.group);
+    }
+};
+
+void load_data(Options& o, HostData& d) {
+    d.off = o.item_offset;
+    std::cout << "Loading train...\t" << std::endl;
+    // A libFM text file whose cases are not all "one user and one item feature" is a general file:
+    // libFM's MCMC / ALS learner reads it as cases with any number of features (sbmf_cases, fmg.cpp);
+    // a two-feature file takes the path it always took.  Binary stems keep the two-feature loaders.
+    const bool text_input = o.libfm_input && o.fmt != "binary" && !has_binary(o.train, o.has_x) && !rowmajor_only(o.train);
+    auto load_or_general = [&](const std::string& path, sbmf_ratings& r) {
+        try {
+            load(path, o.fmt, d.off, o.has_x, r);
+        } catch (const std::runtime_error& e) {
+            if (!text_input || !std::strstr(e.what(), "exactly one user and one item feature per line")) throw;
+            d.general = true;
+        }
+    };
+    load_or_general(o.train, d.tr);
+    std::cout << "Loading test... \t" << std::endl;
+    load_or_general(o.test, d.te);
+    if (d.general) {
+        // refused before any learning: only libFM's own chain is defined on such cases
+        const char* why =
+            o.users.on || o.guests.on ? "-recommend / -recommend_guests rank the items of the SBPMF sampler's user x item model"
+            : o.vb                    ? "-method vb (online VB) updates one user and one item attribute per case"
+            : !o.lfm                  ? "-order sbpmf (the SBPMF sampler) factorizes a user x item rating matrix"
+                                      : nullptr;
+        if (why) fail(std::string("the input holds cases that are not one user and one item feature; ") + why +
+                      ": use -method mcmc (libFM order) or -method als on such a file");
+        sbmf_free_ratings(&d.tr);
+        sbmf_free_ratings(&d.te);
+        if (sbmf_load_libfm_cases(o.train.c_str(), &d.ctr) != SBMF_OK ||
+            sbmf_load_libfm_cases(o.test.c_str(), &d.cte) != SBMF_OK)
+            fail(sbmf_loader_error());
+        d.te_y.assign(d.cte.target, d.cte.target + d.cte.n);
+        d.te.n = d.cte.n;
+        d.te.rating = d.te_y.data();
+        d.te_owns_rating = false;
+    }
+    // libFM's learners (fm_learn_mcmc, fm_learn_vb_online) take the file's feature ids as their attribute ids:
+    // num_user = max first feature id + 1 over train and test (libfm.cpp:219-221,263-265,375) and num_all_attribute
+    // = max feature id + 1 (:328).  With one user and one item feature per line that is the users-first layout with
+    // item offset num_user, so no flag is needed (-item_offset overrides it).
+    // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
+    if ((o.lfm || o.vb || o.users.on || o.guests.on) && o.libfm_input && !o.has_item_offset && !d.general)
+        d.off = users_first_offset(d.tr, d.te);
+    d.ioff = o.libfm_input ? d.off : 0;
+    // -meta and -regular (libFM's learners): one group id per attribute of num_attribute = the
+    // largest feature id over train and test + 2 (libfm.cpp:328-335)
+    uint32_t nmeta_groups = 1;
+    d.grouped = o.lfm && !o.meta.empty();
+    if (d.grouped) {
+        uint64_t na = 0;
+        if (d.general) {
+            na = (uint64_t)std::max(d.ctr.num_attr, d.cte.num_attr) + 1;
+        } else {
+            uint64_t umax = 0, imax = 0;
+            for (const sbmf_ratings* r : {&d.tr, &d.te})
+                for (uint64_t x = 0; x < r->n; ++x) {
+                    umax = std::max<uint64_t>(umax, r->user[x]);
+                    imax = std::max<uint64_t>(imax, r->item[x]);
+                }
+            na = std::max<uint64_t>(d.off, umax + 1) + imax + 2;
+        }
+        if (na > 0xfffffffeull) fail("attribute id too large");
+        d.meta.resize(na);
+        if (sbmf_load_libfm_meta(o.meta.c_str(), (uint32_t)na, d.meta.data(), &nmeta_groups) != SBMF_OK)
+            fail(std::string("-meta: ") + sbmf_loader_error());
+    }
+    for (const std::string& stem : o.rel_stems) {
+        d.rels.emplace_back();
+        RelFiles& r = d.rels.back();
+        if (sbmf_load_libfm_relation(stem.c_str(), &r.block, &r.train_row, &r.n_train, &r.test_row, &r.n_test, &r.group,
+                                     &r.G) != SBMF_OK)
+            fail(std::string("-relation ") + stem + ": " + sbmf_loader_error());
+    }
+    if (!d.rels.empty()) std::cout << "#relations: " << d.rels.size() << std::endl;
+    d.ngroups = nmeta_groups;
+    for (const RelFiles& r : d.rels) d.ngroups += r.G ? r.G : 1;
+    if (o.lfm) parse_regular(o.regular, d.ngroups, o.cfg.reg0, o.cfg.regw, o.cfg.regv, d.greg_w, d.greg_v);
+}
+
+// The list files, all parsed before the context is created.  The guests come after load_data has settled the item
+// offset: their item ids come in the id space -recommend prints (on libFM input the feature id).
+void load_lists(const Options& o, HostData& d) {
+    if (o.users.on) d.rec_ids = read_ids(o.users.in, "-rec_users", "user id");
+    if (o.users.on && d.rec_ids.empty()) fail("-rec_users: " + o.users.in + " lists no user");
+    if (o.guests.on) {
+        unsigned long long it = 0;
+        double r = 0.0;
+        d.guests = read_grouped(
+            o.guests.in, "-rec_guests", "guest item rating", "guest",
+            [&](const char* s, const std::string&, unsigned long long& g) {
+                return std::sscanf(s, "%llu %llu %lf", &g, &it, &r) == 3 && g <= 0xfffffffdull;
+            },
+            [&](const std::string& line) {
+                if (it < d.ioff || it - d.ioff > 0xfffffffeull) fail("-rec_guests: item id out of range in '" + line + "'");
+                d.g_ratings.push_back(r);
+                return (uint32_t)(it - d.ioff);
+            });
+        if (d.guests.ptr.size() < 2) fail("-rec_guests: " + o.guests.in + " lists no guest");
+    }
+    if (!o.queries.on) return;
+    if (sbmf_load_libfm_cases(o.queries.in.c_str(), &d.qcases) != SBMF_OK) fail(std::string("-rec_queries: ") + sbmf_loader_error());
+    const uint64_t nq = d.qcases.n;
+    if (nq == 0) fail("-rec_queries: " + o.queries.in + " lists no query");
+    d.q_rows.resize(o.rel_stems.size());
+    for (size_t r = 0; r < o.rel_stems.size(); ++r) {
+        if (r == o.rec_rel) continue;
+        const std::string qf = o.rel_stems[r] + ".queries";
+        d.q_rows[r] = read_ids(qf, qf, "block row");
+        if (d.q_rows[r].size() != nq)
+            fail(qf + " holds " + std::to_string(d.q_rows[r].size()) + " block rows; -rec_queries " + std::to_string(nq) + " queries");
+    }
+    if (!o.exclude.empty()) {
+        unsigned long long row = 0;
+        d.excl = read_grouped(
+            o.exclude, "-rec_exclude", "query row", "query",
+            [&](const char* s, const std::string& line, unsigned long long& qn) {
+                if (std::sscanf(s, "%llu %llu", &qn, &row) != 2 || row > 0xfffffffeull) return false;
+                if (qn >= nq) fail("-rec_exclude: query number out of range in '" + line + "'");
+                return true;
+            },
+            [&](const std::string&) { return (uint32_t)row; });
+        while (d.excl.ptr.size() < nq + 1) d.excl.ptr.push_back((uint32_t)d.excl.val.size());
+    }
+}
+
+void chk(sbmf_ctx* ctx, int rc) { if (rc != SBMF_OK) fail(sbmf_last_error(ctx)); }
+
+// An error from here on leaves the context as it is: it is destroyed on the success path only (main).
+sbmf_ctx* create_context(const Options& o, HostData& d) {
+    sbmf_ctx* ctx = nullptr;
+    if (sbmf_create(&o.cfg, &ctx) != SBMF_OK) fail(sbmf_last_global_error());
+    if (d.general) {
+        chk(ctx, sbmf_set_train_cases(ctx, &d.ctr));
+        chk(ctx, sbmf_set_test_cases(ctx, &d.cte));
+    } else {
+        chk(ctx, sbmf_set_train(ctx, d.tr.n, d.tr.user, d.tr.item, d.tr.rating));
+        chk(ctx, sbmf_set_test(ctx, d.te.n, d.te.user, d.te.item, d.te.rating));
+        // libFM's attributes are the file's feature ids: users first, items from the (inferred or given) item offset on
+        if ((o.lfm || o.vb) && d.off) chk(ctx, sbmf_set_dims(ctx, d.off, 0));
+    }
+    for (RelFiles& r : d.rels) {
+        chk(ctx, sbmf_add_relation(ctx, &r.block, r.train_row, r.n_train, r.test_row, r.n_test, r.group, r.G));
+        sbmf_free_relation(&r.block, &r.train_row, &r.test_row, &r.group);  // the context holds its own copy
+    }
+    if (d.grouped) chk(ctx, sbmf_set_attr_groups(ctx, (uint32_t)d.meta.size(), d.meta.data()));
+    if (d.joined() && !d.greg_w.empty()) chk(ctx, sbmf_set_group_regular(ctx, d.ngroups, d.greg_w.data(), d.greg_v.data()));
+    chk(ctx, sbmf_prepare(ctx));
+    return ctx;
+}
+
+// "#users= #items= #attributes= #ranges= #train= #test= K=": users and items where the input is one of each per case,
+// attributes and ranges where the general learner runs; before it DataMetaInfo::debug (Data.h:63-68) of joined groups
+void print_dims(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    uint32_t nu, ni, na = 0, nr = 0;
+    uint64_t ntr, nte;
+    chk(ctx, sbmf_get_dims(ctx, &nu, &ni, &ntr, &nte));
+    if (d.joined()) {
+        std::vector<uint32_t> cnt(d.ngroups);
+        uint32_t nattr = (uint32_t)d.meta.size();
+        chk(ctx, sbmf_get_fm_groups(ctx, nullptr, cnt.data(), nullptr, nullptr, nullptr, nullptr));
+        if (!d.rels.empty()) chk(ctx, sbmf_fm_info(ctx, &nattr, nullptr, nullptr));
+        std::cout << "#attr=" << nattr << "\t#groups=" << d.ngroups << std::endl;
+        for (uint32_t g = 0; g < d.ngroups && o.verbosity > 0; ++g)
+            std::cout << "#attr_in_group[" << g << "]=" << cnt[g] << std::endl;
+    }
+    const bool fm = d.general || d.joined();
+    if (fm) chk(ctx, sbmf_fm_info(ctx, &na, &nr, nullptr));
+    if (!d.general) std::cout << "#users=" << nu << "\t#items=" << ni << "\t";
+    if (fm) std::cout << "#attributes=" << na << "\t#ranges=" << nr << "\t";
+    std::cout << "#train=" << ntr << "\t#test=" << nte << "\tK=" << o.cfg.num_factor << std::endl;
+}
+
+// RunState copies what on_sweep and the -rlog columns read: from the options, the loaded data and the context
+void run(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    const sbmf_config& cfg = o.cfg;
+    RunState rs;
+    // libFM names the file after "mcmc" for als too (the als switch rewrites -method, libfm.cpp:133)
+    rs.rmse_file = "test_rmse_" + std::to_string(o.dim[0]) + std::to_string(o.dim[1]) + std::to_string(o.dim[2]) +
+                   (o.vb ? "_vb_online" : "_mcmc");
+    rs.vb = o.vb;
+    rs.lfm = o.lfm;
+    rs.cls = o.cls;
+    rs.G = d.joined() ? d.ngroups : 1;
+    rs.k1 = o.dim[1] != 0;
+    rs.K = cfg.num_factor;
+    rs.ctx = ctx;
+    rs.test = &d.te;
+    rs.avg_collected = !o.lfm && (cfg.average == 1 || (cfg.average == 0 && cfg.quirks == SBMF_QUIRKS_NONE));  // sbmf.cpp avg_collected
+    rs.lo = cfg.clamp_lo >= 0 ? cfg.clamp_lo : (cfg.quirks == SBMF_QUIRKS_SBPMF2 || cfg.quirks == SBMF_QUIRKS_BIAS2 ? 0.5 : 1.0);
+    rs.hi = cfg.clamp_hi;
+    // libFM clamps to the train target range instead (libfm.cpp:459-460)
+    auto range = [&](const auto* y, uint64_t n) { rs.lo = *std::min_element(y, y + n), rs.hi = *std::max_element(y, y + n); };
+    if (d.general) range(d.ctr.target, d.ctr.n);
+    else if (o.lfm) range(d.tr.rating, d.tr.n);
+    { std::ofstream trunc(rs.rmse_file); }
+    std::ofstream rlog;
+    if (!o.rlog.empty()) {
+        rlog.open(o.rlog);
+        if (!rlog.is_open()) fail("Unable to open file " + o.rlog);
+        std::cout << "logging to " << o.rlog << std::endl;
+        rlog_header(rlog, rs);
+        rs.rlog = &rlog;
+    }
+    rs.verbosity = o.verbosity;
+    if (o.users.on) chk(ctx, sbmf_watch_users(ctx, (uint32_t)d.rec_ids.size(), d.rec_ids.data(), 0));
+    if (o.guests.on)
+        chk(ctx, sbmf_foldin_users(ctx, (uint32_t)d.guests.ptr.size() - 1, d.guests.ptr.data(), d.guests.val.data(),
+                                   d.g_ratings.data(), 0));
+    if (o.queries.on) {
+        std::vector<const uint32_t*> rp(o.rel_stems.size(), nullptr);
+        for (size_t r = 0; r < o.rel_stems.size(); ++r)
+            if (r != o.rec_rel) rp[r] = d.q_rows[r].data();
+        const bool none = d.excl.val.empty();  // no -rec_exclude, or one that lists nothing
+        chk(ctx, sbmf_fm_query_cases(ctx, (uint32_t)o.rec_rel, &d.qcases, rp.data(), none ? nullptr : d.excl.ptr.data(),
+                                     none ? nullptr : d.excl.val.data(), 0));
+    }
+    chk(ctx, sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
+}
+
+// One top-N file: `recommend` fills topn slots per row of its list; every filled slot is a line
+// "row<TAB>item<TAB>mean<TAB>stdev", the row as its id (`ids`) or else its number, the item moved by ioff
+using Recommend = int (*)(sbmf_ctx*, uint32_t, uint32_t, double, uint32_t*, double*, double*);
+void write_topn(sbmf_ctx* ctx, Recommend recommend, const Options& o, const std::string& path, size_t rows,
+                const uint32_t* ids, uint64_t ioff) {
+    const size_t topn = (size_t)o.topn, slots = rows * topn;
+    std::vector<uint32_t> it(slots);
+    std::vector<double> mean(slots), sd(slots);
+    chk(ctx, recommend(ctx, (uint32_t)topn, 0, o.risk, it.data(), mean.data(), sd.data()));
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) fail("Unable to open file " + path);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < topn; ++k) {
+            const size_t x = r * topn + k;
+            if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
+            ids ? std::fprintf(f, "%u", ids[r]) : std::fprintf(f, "%zu", r);
+            std::fprintf(f, "\t%llu\t%.17g\t%.17g\n", (unsigned long long)(it[x] + ioff), mean[x], sd[x]);
+        }
+    std::fclose(f);
+}
+
+void write_outputs(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    // queries, then users, then guests; ids as in the input files: on libFM input the item's feature id
+    if (o.queries.on) write_topn(ctx, sbmf_fm_query_recommend, o, o.queries.out, d.qcases.n, nullptr, 0);
+    if (o.users.on) write_topn(ctx, sbmf_recommend, o, o.users.out, d.rec_ids.size(), d.rec_ids.data(), d.ioff);
+    if (o.guests.on) write_topn(ctx, sbmf_foldin_recommend, o, o.guests.out, d.guests.ptr.size() - 1, nullptr, d.ioff);
+    if (!o.out.empty()) {
+        uint64_t nte = 0;
+        chk(ctx, sbmf_get_dims(ctx, nullptr, nullptr, nullptr, &nte));
+        std::vector<double> pred(nte);
+        chk(ctx, sbmf_predict(ctx, pred.data()));
+        std::ofstream out(o.out);
+        for (double p : pred) out << p << "\n";
+    }
+}
+
+// SBMF_EXIT=guard (opt-in; round 3's default): leave through sbmf_exit_guard's
+// handler (registered at main's start, before the first HIP call), so a profiler's
+// exit handlers still run and the shared-library finalizers do not.  The finalizer
+// fault it skipped under rocprofv3 came with RCCL linked at load time; libsbmf
+// dlopens RCCL only for a multi-GPU communicator now, and the CLI exits normally
+// under rocprofv3 (profiles/r04/r04s2_cli_rocprof_kernel_stats.csv, DESIGN.md §10).
 bool g_guarded = false;
 int leave(int rc) {
     std::cout.flush();
@@ -410,586 +973,21 @@ int main(int argc, char** argv) {
         std::cout << "----------------------------------------------------------------------------\n"
                   << "sbmf -- Scalable-BPMF Gibbs sampler for AMD Instinct MI355X (libFM command line)\n"
                   << "----------------------------------------------------------------------------" << std::endl;
-        // libFM's flags (libfm.cpp:86-111)
-        cl.reg("task", "r=regression, c=binary classification (libFM's probit model: targets <= 0 are the negative "
-                       "class; -method als and -method mcmc in libFM order only) [MANDATORY]");
-        cl.reg("meta", "filename with one attribute group id per attribute (libFM's -meta): -method mcmc (libFM order) "
-                       "and -method als draw their hyperparameters per group, and a two-feature input then takes the "
-                       "general learner; ignored by the SBPMF sampler (-order sbpmf: one user and one item group) and "
-                       "by -method vb");
-        cl.reg("train", "filename for training data [MANDATORY] (SBPMF triples or libFM text)");
-        cl.reg("test", "filename for test data [MANDATORY]");
-        cl.reg("validation", "unused (SGDA only in libFM)");
-        cl.reg("out", "filename for output: averaged test predictions");
-        cl.reg("dim", "'k0,k1,k2': k0=use bias, k1=use 1-way interactions, k2=dim of 2-way interactions; default=1,1,8");
-        cl.reg("regular", "'r0,r1,r2' (or one value for all) for -method als and -method mcmc -order libfm: "
-                          "fixed / starting precisions of w0, w, v (libfm.cpp:484-513); with the G groups of -meta also "
-                          "'r0,w[0],..,w[G-1],v[0],..,v[G-1]' (1 + 2G values, :514-521); default=0");
-        cl.reg("init_stdev", "stdev for initialization of the factors; default: 1.0 (quirks final) / 0.1 (sbpmf2)");
-        cl.reg("stdev", "unused");
-        cl.reg("iter", "number of collection sweeps; default=100");
-        cl.reg("learn_rate", "unused (SGD only)");
-        cl.reg("method", "learning method: mcmc (SBPMF Gibbs; with -order libfm libFM's own MCMC chain) | "
-                         "als (libFM's ALS) | vb (online variational Bayes, libFM's vb_online; alias vb_online); "
-                         "default=mcmc");
-        cl.reg("order", "-method mcmc: libfm (libFM's fm_learn_mcmc chain: f-outer, one hyperprior group, w0 / w "
-                        "per -dim k0,k1, sqrt(variance) stdev; default on libFM text / binary input, as bin/libFM) | "
-                        "sbpmf (the SBPMF sampler of gibbs_sbpmf_final.cpp; default on SBPMF triple input)");
-        cl.reg("verbosity", "how much infos to print; default=0");
-        cl.reg("rlog", "write per-sweep measurements to a TSV file; default=''");
-        cl.reg("seed", "integer seed; default=1 (glibc default seed of the reference samplers)");
-        cl.reg("help", "this screen");
-        cl.reg("relation", "BS: comma-separated stems of block-structure relations (libFM's -relation: <stem>.xt or .x, "
-                           "<stem>.train, <stem>.test, optional <stem>.groups): -method mcmc (libFM order) and -method als");
-        cl.reg("cache_size", "unused (binary data format)");
-        // sampler settings
-        cl.reg("rng", "ref (reference glibc/Leva/Marsaglia-Tsang stream; default) | philox (in-kernel, throughput)");
-        cl.reg("quirks", "final (gibbs_sbpmf_final.cpp; default) | sbpmf2 | none (stdev = sqrt(variance)) | bias2 | bias22 "
-                         "(biased sampler, top-level gibbs_sbpmf2.cpp / gibbs_sbpmf22.cpp; needs -dim '1,1,K')");
-        cl.reg("precision", "f64 (default) | f32");
-        cl.reg("burnin", "burn-in sweeps before collection; default=0");
-        cl.reg("average", "running-mean divisor: default (quirk set) | collected (collected sweeps only) | "
-                          "reference (sweep + 1, counts burn-in as gibbs_sbpmf_final.cpp:559 does)");
-        cl.reg("format", "auto (default: libFM's binary files if present -- <name>.xt/.y or .datat/.target for "
-                          "-method mcmc|als, <name>.x/.xt/.y or .data/.datat/.target for vb (Data.h:112-117) --, else "
-                          "triple or libfm text) | triple | libfm | binary");
-        cl.reg("item_offset", "libFM input: item feature id offset; default: libFM's num_user (max user feature "
-                              "id + 1, libfm.cpp:375) for -method mcmc (libFM order) / als / vb, 0 for -order sbpmf");
-        cl.reg("device", "HIP device ordinal; default=0");
-        cl.reg("recompute_every", "recompute residuals from scratch every n sweeps; default=1");
-        cl.reg("stream_threshold", "rows with more ratings take the streaming kernel; default=256 (f64) / 512 (f32)");
-        cl.reg("split_chunk", "streaming task size; longer rows are split into chunks on several workgroups; default: "
-                              "the register capacity of the workgroup shape (512 / 1024 / 2048 f64 ratings for 4 / 8 / "
-                              "16 waves), larger values are capped to it");
-        // posterior top-N for a list of users (sbmf_watch_users / sbmf_recommend)
-        cl.reg("recommend", "filename for output: per user of -rec_users the -rec_topn unrated items with the largest "
-                            "posterior mean score (less -rec_risk stdevs), one 'user<TAB>item<TAB>mean<TAB>stdev' line "
-                            "each, ids as in the input files; the SBPMF sampler only (-method mcmc -order sbpmf); on "
-                            "libFM input the item offset then defaults to libFM's num_user");
-        cl.reg("rec_users", "filename with one user id per line [MANDATORY with -recommend]");
-        cl.reg("rec_topn", "items per user, 1..1024; default=10");
-        cl.reg("rec_risk", "rank by mean - x * stdev (a lower confidence bound for x > 0); default=0");
-        // the same for guests: users outside the training set (sbmf_foldin_users / sbmf_foldin_recommend)
-        cl.reg("rec_guests", "filename with one 'guest item rating' line per rating of a user outside the training "
-                             "set: guests numbered from 0, the numbers non-decreasing (a skipped number is a guest "
-                             "without ratings), item ids as -recommend prints them [MANDATORY with -recommend_guests]");
-        cl.reg("recommend_guests", "filename for output: -recommend's lines for the guests of -rec_guests ('guest<TAB>"
-                                   "item<TAB>mean<TAB>stdev', the guest's own items left out); shares -rec_topn and "
-                                   "-rec_risk; the SBPMF sampler with the unbiased quirk sets only");
-        // the libFM learner's query list (sbmf_fm_query_cases / sbmf_fm_query_recommend)
-        cl.reg("recommend_queries", "filename for output: per query of -rec_queries the -rec_topn block rows of the "
-                                    "relation -rec_relation with the largest posterior mean prediction (less -rec_risk "
-                                    "stdevs), one 'query<TAB>row<TAB>mean<TAB>stdev' line each; -method mcmc (libFM order) "
-                                    "or als with -relation only");
-        cl.reg("rec_queries", "filename with the queries' main-table features in libFM text format (the target column is "
-                              "ignored); for every relation but -rec_relation's, <stem>.queries holds the block row of "
-                              "each query, one per line [MANDATORY with -recommend_queries]");
-        cl.reg("rec_relation", "the relation whose block rows are ranked: one of -relation's stems [MANDATORY with "
-                               "-recommend_queries]");
-        cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
-                              "numbers non-decreasing");
+        register_flags(cl);
         if (cl.has("help") || argc == 1) {
             cl.print_help();
             return leave(0);
         }
         cl.check();
-        const std::string task = cl.get("task", "");
-        const char* task_refusal = "only -task r (regression) is supported by the SBPMF sampler";
-        if (task != "r" && task != "c") throw std::runtime_error(task_refusal);
-        const bool cls = task == "c";
-        const std::string method = cl.get("method", "mcmc");
-        const bool vb = method == "vb" || method == "vb_online";
-        // -task c is libFM's MCMC / ALS learner's: every other route is refused before a file is
-        // looked at where the flags alone decide it (-method vb, -order sbpmf, -quirks, triple input)
-        if (cls && (vb || cl.get("order", "") == "sbpmf" || (cl.has("quirks") && !cl.has("order")) ||
-                    cl.get("format", "auto") == "triple"))
-            throw std::runtime_error(task_refusal);
-        const bool rec = cl.has("recommend");
-        const char* rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
-        if (rec && cl.get("recommend", "").empty()) throw std::runtime_error("-recommend needs a file name");
-        if (rec && cl.get("rec_users", "").empty())
-            throw std::runtime_error("-recommend needs -rec_users <file> (one user id per line)");
-        const bool recg = cl.has("recommend_guests");
-        const char* recg_refusal = "-recommend_guests is offered by the SBPMF sampler (-method mcmc -order sbpmf) with "
-                                   "the unbiased quirk sets (final, sbpmf2, none)";
-        if (recg && cl.get("recommend_guests", "").empty()) throw std::runtime_error("-recommend_guests needs a file name");
-        if (recg && cl.get("rec_guests", "").empty())
-            throw std::runtime_error("-recommend_guests needs -rec_guests <file> ('guest item rating' per line)");
-        if (!recg && cl.has("rec_guests")) throw std::runtime_error("-rec_guests goes with -recommend_guests <file>");
-        if (!rec && cl.has("rec_users")) throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
-        const bool recq = cl.has("recommend_queries");
-        const char* recq_refusal = "-recommend_queries is offered by libFM's MCMC / ALS learner (-method mcmc -order libfm, "
-                                   "-method als) with -relation: it ranks the block rows of one relation";
-        if (recq && cl.get("recommend_queries", "").empty()) throw std::runtime_error("-recommend_queries needs a file name");
-        if (!recq && (cl.has("rec_queries") || cl.has("rec_relation") || cl.has("rec_exclude")))
-            throw std::runtime_error("-rec_queries / -rec_relation / -rec_exclude go with -recommend_queries <file>");
-        if (recq && cl.get("rec_queries", "").empty())
-            throw std::runtime_error("-recommend_queries needs -rec_queries <file> (the queries in libFM text format)");
-        if (recq && cl.get("rec_relation", "").empty())
-            throw std::runtime_error("-recommend_queries needs -rec_relation <stem> (one of -relation's stems)");
-        if (recq && vb) throw std::runtime_error(recq_refusal);  // before any file is opened
-        std::vector<std::string> rel_stems;
-        {
-            std::stringstream ss(cl.get("relation", ""));
-            std::string stem;
-            while (std::getline(ss, stem, ','))
-                if (!stem.empty()) rel_stems.push_back(stem);
-        }
-        size_t rec_rel = 0;
-        if (recq) {
-            if (rel_stems.empty()) throw std::runtime_error(recq_refusal);
-            rec_rel = std::find(rel_stems.begin(), rel_stems.end(), cl.get("rec_relation", "")) - rel_stems.begin();
-            if (rec_rel == rel_stems.size())
-                throw std::runtime_error("-rec_relation " + cl.get("rec_relation", "") + " names none of -relation's stems (" +
-                                         cl.get("relation", "") + ")");
-        }
-        if (!rec && !recg && !recq && (cl.has("rec_topn") || cl.has("rec_risk")))
-            throw std::runtime_error("-rec_users / -rec_topn / -rec_risk go with -recommend");
-        if (rec && method != "mcmc") throw std::runtime_error(rec_refusal);  // before any file is opened
-        if (recg && method != "mcmc") throw std::runtime_error(recg_refusal);
-        const long rec_topn = cl.getl("rec_topn", 10);
-        if ((rec || recg || recq) && (rec_topn < 1 || rec_topn > 1024)) throw std::runtime_error("-rec_topn must be in 1..1024");
-        const std::string fmt = cl.get("format", "auto");
-        if (fmt != "auto" && fmt != "triple" && fmt != "libfm" && fmt != "binary")
-            throw std::runtime_error("unknown -format " + fmt);
-        // bin/libFM -method mcmc runs fm_learn_mcmc on libFM data (libfm.cpp:411-419); the SBPMF
-        // sampler reads the triple files of gibbs_sbpmf_final.cpp:43
-        const std::string trainf = cl.get("train", "");
-        // the MCMC and ALS sets carry no row-major data (libfm.cpp:140-149): they read the transpose
-        const bool has_x = vb;
-        const bool libfm_input = fmt == "libfm" || fmt == "binary" ||
-                                 (fmt == "auto" && (has_binary(trainf, has_x) || rowmajor_only(trainf) ||
-                                                    looks_libfm(trainf)));
-        const std::string order = cl.get("order", libfm_input ? "libfm" : "sbpmf");
-        if (order != "sbpmf" && order != "libfm") throw std::runtime_error("unknown -order " + order);
-        const bool als = method == "als";
-        const std::string q = cl.get("quirks", "final");
-        const bool biased = q == "bias2" || q == "bias22";
-        // libFM's fm_learn_mcmc learner; -quirks (the SBPMF samplers' variants) selects the SBPMF sampler
-        const bool lfm = als || (method == "mcmc" && order == "libfm" && !(cl.has("quirks") && !cl.has("order")));
-        if (cls && !lfm) throw std::runtime_error(task_refusal);
-        // unlike -meta, -relation cannot be ignored: the relations' features would be missing (before any file is opened)
-        if (!lfm && !cl.get("relation", "").empty())
-            throw std::runtime_error(std::string("-relation: block-structure relations are drawn by libFM's MCMC / ALS learner "
-                                                 "(-method mcmc -order libfm, -method als); ") +
-                                     (vb ? "-method vb (online VB)" : "-method mcmc -order sbpmf (the SBPMF sampler)") +
-                                     " does not read them, and without them the relations' features would be missing");
-        if (rec && lfm) throw std::runtime_error(rec_refusal);
-        if (recq && !lfm) throw std::runtime_error(recq_refusal);
-        if (recg && (lfm || biased)) throw std::runtime_error(recg_refusal);  // (a guest bias would need its own draw)
-        if (method != "mcmc" && !vb && !als)
-            throw std::runtime_error("-method " + method + " is not supported (use mcmc, als or vb)");
-        if (!cl.has("train") || !cl.has("test")) throw std::runtime_error("-train and -test are mandatory");
-        std::vector<int> dim = split_ints(cl.get("dim", "1,1,8"));
-        if (dim.size() != 3) throw std::runtime_error("dim must have 3 numbers");
-        if (dim[2] <= 0 || dim[2] > 256) throw std::runtime_error("dim k2 must be in [1,256]");
-        if (vb && !(dim[0] == 1 && dim[1] == 1))
-            throw std::runtime_error("the online VB learner updates w0 and the user/item w: use -dim '1,1,K'");
-        if (lfm && biased) throw std::runtime_error("-quirks bias2|bias22 selects the SBPMF biased sampler, not libFM's");
-        if (!vb && !lfm && !biased && (dim[0] || dim[1]))  // stdout stays libFM's
-            std::cerr << "note: -order sbpmf: bias terms (k0,k1) are not sampled; the reference SBPMF sampler has "
-                         "them compiled out (gibbs_sbpmf_final.cpp:276-295); -quirks bias2|bias22 selects the biased "
-                         "sampler, -order libfm libFM's own chain"
-                      << std::endl;
-        if (biased && !(dim[0] == 1 && dim[1] == 1))
-            throw std::runtime_error("the biased sampler (gibbs_sbpmf2.cpp) samples b0 and the user/item biases: "
-                                     "use -dim '1,1,K'");
-
-        sbmf_config cfg;
-        sbmf_config_default(&cfg);
-        cfg.num_factor = (uint32_t)dim[2];
-        cfg.num_iter = (uint32_t)cl.getl("iter", 100);
-        cfg.burnin = (uint32_t)cl.getl("burnin", 0);
-        {
-            const std::string av = cl.get("average", "default");
-            if (av == "default") cfg.average = 0;
-            else if (av == "collected") cfg.average = 1;
-            else if (av == "reference") cfg.average = 2;
-            else throw std::runtime_error("unknown -average " + av);
-        }
-        cfg.seed = (uint64_t)cl.getl("seed", 1);
-        const std::string rng = cl.get("rng", "ref");
-        cfg.rng_mode = rng == "philox" ? SBMF_RNG_PHILOX : SBMF_RNG_REFERENCE;
-        // on_sweep prints and appends to files, never stops the run and reads no device state: in
-        // Philox mode the next sweep's start is queued before it runs (sbmf_config.pipeline)
-        cfg.pipeline = 1;
-        if (q == "sbpmf2")
-            cfg.quirks = SBMF_QUIRKS_SBPMF2;
-        else if (q == "none")
-            cfg.quirks = SBMF_QUIRKS_NONE;
-        else if (q == "bias2")
-            cfg.quirks = SBMF_QUIRKS_BIAS2;
-        else if (q == "bias22")
-            cfg.quirks = SBMF_QUIRKS_BIAS22;
-        else if (q == "final")
-            cfg.quirks = SBMF_QUIRKS_FINAL;
-        else
-            throw std::runtime_error("unknown -quirks " + q);
-        cfg.precision = cl.get("precision", "f64") == "f32" ? SBMF_F32 : SBMF_F64;
-        cfg.device = (int32_t)cl.getl("device", 0);
-        if (cl.has("init_stdev")) cfg.init_stdev = cl.getd("init_stdev", 1.0);
-        cfg.recompute_every = (uint32_t)cl.getl("recompute_every", 1);
-        cfg.stream_threshold = (uint32_t)cl.getl("stream_threshold", 0);
-        cfg.split_chunk = (uint32_t)cl.getl("split_chunk", 0);
-        cfg.eval_train = vb ? 0 : 1;
-        cfg.method = vb ? SBMF_METHOD_VB : als ? SBMF_METHOD_ALS : lfm ? SBMF_METHOD_LIBFM_MCMC : SBMF_METHOD_MCMC;
-        cfg.task = cls ? SBMF_TASK_CLASSIFICATION : SBMF_TASK_REGRESSION;
-        if (lfm) {
-            cfg.libfm_dim = (dim[0] ? 1u : 0u) | (dim[1] ? 2u : 0u);
-            if (!cl.has("init_stdev")) cfg.init_stdev = 0.1;  // libfm.cpp:127
-        }
-        cfg.eval_test = 1;
-
-        uint32_t off = (uint32_t)cl.getl("item_offset", 0);
-        std::cout << "Loading train...\t" << std::endl;
-        sbmf_ratings tr{}, te{};
-        // A libFM text file whose cases are not all "one user and one item feature" is a general file:
-        // libFM's MCMC / ALS learner reads it as cases with any number of features (sbmf_cases, fmg.cpp);
-        // a two-feature file takes the path it always took.  Binary stems keep the two-feature loaders.
-        const bool text_input = libfm_input && fmt != "binary" && !has_binary(trainf, has_x) && !rowmajor_only(trainf);
-        bool general = false;
-        auto load_or_general = [&](const std::string& path, sbmf_ratings& r) {
-            try {
-                load(path, fmt, off, has_x, r);
-            } catch (const std::runtime_error& e) {
-                if (!text_input || !std::strstr(e.what(), "exactly one user and one item feature per line")) throw;
-                general = true;
-            }
-        };
-        load_or_general(cl.get("train", ""), tr);
-        std::cout << "Loading test... \t" << std::endl;
-        load_or_general(cl.get("test", ""), te);
-        sbmf_cases ctr{}, cte{};
-        if (general) {
-            // refused before any learning: only libFM's own chain is defined on such cases
-            const char* why = nullptr;
-            if (rec || recg)
-                why = "-recommend / -recommend_guests rank the items of the SBPMF sampler's user x item model";
-            else if (vb)
-                why = "-method vb (online VB) updates one user and one item attribute per case";
-            else if (!lfm)
-                why = "-order sbpmf (the SBPMF sampler) factorizes a user x item rating matrix";
-            if (why)
-                throw std::runtime_error(std::string("the input holds cases that are not one user and one item feature; ") +
-                                         why + ": use -method mcmc (libFM order) or -method als on such a file");
-            sbmf_free_ratings(&tr);
-            sbmf_free_ratings(&te);
-            if (sbmf_load_libfm_cases(cl.get("train", "").c_str(), &ctr) != SBMF_OK ||
-                sbmf_load_libfm_cases(cl.get("test", "").c_str(), &cte) != SBMF_OK)
-                throw std::runtime_error(sbmf_loader_error());
-        }
-        // libFM's learners (fm_learn_mcmc, fm_learn_vb_online) take the file's feature ids as
-        // their attribute ids: num_user = max first feature id + 1 over train and test
-        // (libfm.cpp:219-221,263-265,375) and num_all_attribute = max feature id + 1 (:328).
-        // With one user and one item feature per line that is the users-first layout with
-        // item offset num_user, so no flag is needed (-item_offset overrides it).
-        // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
-        if ((lfm || vb || rec || recg) && libfm_input && !cl.has("item_offset") && !general) off = users_first_offset(tr, te);
-        // -meta and -regular (libFM's learners): one group id per attribute of num_attribute = the
-        // largest feature id over train and test + 2 (libfm.cpp:328-335)
-        std::vector<uint32_t> meta;
-        std::vector<double> greg_w, greg_v;
-        uint32_t nmeta_groups = 1;
-        const bool grouped = lfm && cl.has("meta") && !cl.get("meta", "").empty();
-        if (grouped) {
-            uint64_t na = 0;
-            if (general) {
-                na = (uint64_t)std::max(ctr.num_attr, cte.num_attr) + 1;
-            } else {
-                uint64_t umax = 0, imax = 0;
-                for (const sbmf_ratings* r : {&tr, &te})
-                    for (uint64_t x = 0; x < r->n; ++x) {
-                        umax = std::max<uint64_t>(umax, r->user[x]);
-                        imax = std::max<uint64_t>(imax, r->item[x]);
-                    }
-                na = std::max<uint64_t>(off, umax + 1) + imax + 2;
-            }
-            if (na > 0xfffffffeull) throw std::runtime_error("attribute id too large");
-            meta.resize(na);
-            if (sbmf_load_libfm_meta(cl.get("meta", "").c_str(), (uint32_t)na, meta.data(), &nmeta_groups) != SBMF_OK)
-                throw std::runtime_error(std::string("-meta: ") + sbmf_loader_error());
-        }
-        // -relation (libfm.cpp:301-322): the block tables and the maps of the train / test cases
-        struct RelFiles {
-            sbmf_cases block{};
-            uint32_t *train_row = nullptr, *test_row = nullptr, *group = nullptr;
-            uint64_t n_train = 0, n_test = 0;
-            uint32_t G = 0;
-        };
-        std::vector<RelFiles> rels;
-        {
-            std::stringstream ss(cl.get("relation", ""));
-            std::string stem;
-            while (std::getline(ss, stem, ','))
-                if (!stem.empty()) {
-                    rels.emplace_back();
-                    RelFiles& r = rels.back();
-                    if (sbmf_load_libfm_relation(stem.c_str(), &r.block, &r.train_row, &r.n_train, &r.test_row, &r.n_test,
-                                                 &r.group, &r.G) != SBMF_OK)
-                        throw std::runtime_error(std::string("-relation ") + stem + ": " + sbmf_loader_error());
-                }
-        }
-        if (!rels.empty()) std::cout << "#relations: " << rels.size() << std::endl;
-        uint32_t ngroups = nmeta_groups;  // the joined groups: the main table's, then every relation's
-        for (const RelFiles& r : rels) ngroups += r.G ? r.G : 1;
-        if (lfm) parse_regular(cl.get("regular", ""), ngroups, cfg.reg0, cfg.regw, cfg.regv, greg_w, greg_v);
-        std::vector<uint32_t> rec_ids;
-        if (rec) {
-            std::ifstream f(cl.get("rec_users", ""));
-            if (!f.is_open()) throw std::runtime_error("Unable to open file " + cl.get("rec_users", ""));
-            std::string line;
-            while (std::getline(f, line)) {
-                const size_t p = line.find_first_not_of(" \t\r");
-                if (p == std::string::npos || line[p] == '#') continue;
-                char* end = nullptr;
-                const unsigned long long v = std::strtoull(line.c_str() + p, &end, 10);
-                if (end == line.c_str() + p || v > 0xfffffffeull)
-                    throw std::runtime_error("-rec_users: cannot read a user id from '" + line + "'");
-                rec_ids.push_back((uint32_t)v);
-            }
-            if (rec_ids.empty()) throw std::runtime_error("-rec_users: " + cl.get("rec_users", "") + " lists no user");
-        }
-        // the guests' CSR; item ids come in the id space -recommend prints (on libFM input the feature id)
-        std::vector<uint32_t> g_ptr, g_items;
-        std::vector<double> g_ratings;
-        if (recg) {
-            const std::string gf = cl.get("rec_guests", "");
-            std::ifstream f(gf);
-            if (!f.is_open()) throw std::runtime_error("Unable to open file " + gf);
-            const unsigned long long ioff = libfm_input ? off : 0;
-            std::string line;
-            g_ptr.push_back(0);
-            while (std::getline(f, line)) {
-                const size_t p = line.find_first_not_of(" \t\r");
-                if (p == std::string::npos || line[p] == '#') continue;
-                unsigned long long g = 0, it = 0;
-                double r = 0.0;
-                if (std::sscanf(line.c_str() + p, "%llu %llu %lf", &g, &it, &r) != 3 || g > 0xfffffffdull)
-                    throw std::runtime_error("-rec_guests: cannot read 'guest item rating' from '" + line + "'");
-                if (g + 2 < g_ptr.size())  // the open guest is number g_ptr.size() - 2
-                    throw std::runtime_error("-rec_guests: guest numbers must not decrease ('" + line + "')");
-                if (it < ioff || it - ioff > 0xfffffffeull)
-                    throw std::runtime_error("-rec_guests: item id out of range in '" + line + "'");
-                while (g_ptr.size() < g + 2) g_ptr.push_back((uint32_t)g_items.size());  // opens guest g (and skipped ones)
-                g_items.push_back((uint32_t)(it - ioff));
-                g_ratings.push_back(r);
-                g_ptr.back() = (uint32_t)g_items.size();
-            }
-            if (g_ptr.size() < 2) throw std::runtime_error("-rec_guests: " + gf + " lists no guest");
-        }
-
-        // the queries: their main features, a block row of every relation but the candidates', the exclusions
-        sbmf_cases qcases{};
-        std::vector<std::vector<uint32_t>> q_rows(rel_stems.size());
-        std::vector<uint32_t> q_eptr, q_erows;
-        if (recq) {
-            if (sbmf_load_libfm_cases(cl.get("rec_queries", "").c_str(), &qcases) != SBMF_OK)
-                throw std::runtime_error(std::string("-rec_queries: ") + sbmf_loader_error());
-            if (qcases.n == 0) throw std::runtime_error("-rec_queries: " + cl.get("rec_queries", "") + " lists no query");
-            for (size_t r = 0; r < rel_stems.size(); ++r) {
-                if (r == rec_rel) continue;
-                const std::string qf = rel_stems[r] + ".queries";
-                std::ifstream f(qf);
-                if (!f.is_open()) throw std::runtime_error("Unable to open file " + qf);
-                std::string line;
-                while (std::getline(f, line)) {
-                    const size_t p = line.find_first_not_of(" \t\r");
-                    if (p == std::string::npos || line[p] == '#') continue;
-                    char* end = nullptr;
-                    const unsigned long long v = std::strtoull(line.c_str() + p, &end, 10);
-                    if (end == line.c_str() + p || v > 0xfffffffeull)
-                        throw std::runtime_error(qf + ": cannot read a block row from '" + line + "'");
-                    q_rows[r].push_back((uint32_t)v);
-                }
-                if (q_rows[r].size() != qcases.n)
-                    throw std::runtime_error(qf + " holds " + std::to_string(q_rows[r].size()) + " block rows; -rec_queries " +
-                                             std::to_string(qcases.n) + " queries");
-            }
-            if (cl.has("rec_exclude") && !cl.get("rec_exclude", "").empty()) {
-                const std::string ef = cl.get("rec_exclude", "");
-                std::ifstream f(ef);
-                if (!f.is_open()) throw std::runtime_error("Unable to open file " + ef);
-                std::string line;
-                q_eptr.push_back(0);
-                while (std::getline(f, line)) {
-                    const size_t p = line.find_first_not_of(" \t\r");
-                    if (p == std::string::npos || line[p] == '#') continue;
-                    unsigned long long qn = 0, row = 0;
-                    if (std::sscanf(line.c_str() + p, "%llu %llu", &qn, &row) != 2 || row > 0xfffffffeull)
-                        throw std::runtime_error("-rec_exclude: cannot read 'query row' from '" + line + "'");
-                    if (qn >= qcases.n) throw std::runtime_error("-rec_exclude: query number out of range in '" + line + "'");
-                    if (qn + 2 < q_eptr.size())
-                        throw std::runtime_error("-rec_exclude: query numbers must not decrease ('" + line + "')");
-                    while (q_eptr.size() < qn + 2) q_eptr.push_back((uint32_t)q_erows.size());
-                    q_erows.push_back((uint32_t)row);
-                    q_eptr.back() = (uint32_t)q_erows.size();
-                }
-                while (q_eptr.size() < qcases.n + 1) q_eptr.push_back((uint32_t)q_erows.size());
-            }
-        }
-
-        sbmf_ctx* ctx = nullptr;
-        if (sbmf_create(&cfg, &ctx) != SBMF_OK) throw std::runtime_error(sbmf_last_global_error());
-        auto chk = [&](int rc) {
-            if (rc != SBMF_OK) throw std::runtime_error(sbmf_last_error(ctx));
-        };
-        std::vector<double> te_y;  // general input: the test targets as the -rlog evaluation reads them
-        if (general) {
-            chk(sbmf_set_train_cases(ctx, &ctr));
-            chk(sbmf_set_test_cases(ctx, &cte));
-            te_y.assign(cte.target, cte.target + cte.n);
-            te.n = cte.n;
-            te.rating = te_y.data();
-        } else {
-            chk(sbmf_set_train(ctx, tr.n, tr.user, tr.item, tr.rating));
-            chk(sbmf_set_test(ctx, te.n, te.user, te.item, te.rating));
-            // libFM's attributes are the file's feature ids: users first, items from the
-            // (inferred or given) item offset on
-            if ((lfm || vb) && off) chk(sbmf_set_dims(ctx, off, 0));
-        }
-        for (RelFiles& r : rels) {
-            chk(sbmf_add_relation(ctx, &r.block, r.train_row, r.n_train, r.test_row, r.n_test, r.group, r.G));
-            sbmf_free_relation(&r.block, &r.train_row, &r.test_row, &r.group);
-        }
-        if (grouped) chk(sbmf_set_attr_groups(ctx, (uint32_t)meta.size(), meta.data()));
-        if ((grouped || !rels.empty()) && !greg_w.empty())
-            chk(sbmf_set_group_regular(ctx, ngroups, greg_w.data(), greg_v.data()));
-        chk(sbmf_prepare(ctx));
-        uint32_t nu, ni;
-        uint64_t ntr, nte;
-        chk(sbmf_get_dims(ctx, &nu, &ni, &ntr, &nte));
-        if (grouped || !rels.empty()) {  // DataMetaInfo::debug (Data.h:63-68) of the joined table
-            std::vector<uint32_t> cnt(ngroups);
-            uint32_t na = (uint32_t)meta.size();
-            chk(sbmf_get_fm_groups(ctx, nullptr, cnt.data(), nullptr, nullptr, nullptr, nullptr));
-            if (!rels.empty()) chk(sbmf_fm_info(ctx, &na, nullptr, nullptr));
-            std::cout << "#attr=" << na << "\t#groups=" << ngroups << std::endl;
-            for (uint32_t g = 0; g < ngroups && cl.getl("verbosity", 0) > 0; ++g)
-                std::cout << "#attr_in_group[" << g << "]=" << cnt[g] << std::endl;
-        }
-        if (!general && (grouped || !rels.empty())) {  // the triples through the general learner
-            uint32_t na = 0, nr = 0;
-            chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
-            std::cout << "#users=" << nu << "\t#items=" << ni << "\t#attributes=" << na << "\t#ranges=" << nr
-                      << "\t#train=" << ntr << "\t#test=" << nte << "\tK=" << cfg.num_factor << std::endl;
-        } else if (general) {
-            uint32_t na = 0, nr = 0;
-            chk(sbmf_fm_info(ctx, &na, &nr, nullptr));
-            std::cout << "#attributes=" << na << "\t#ranges=" << nr << "\t#train=" << ntr << "\t#test=" << nte
-                      << "\tK=" << cfg.num_factor << std::endl;
-        } else {
-            std::cout << "#users=" << nu << "\t#items=" << ni << "\t#train=" << ntr << "\t#test=" << nte
-                      << "\tK=" << cfg.num_factor << std::endl;
-        }
-
-        RunState rs;
-        std::ostringstream nm;
-        nm << dim[0] << dim[1] << dim[2];
-        // libFM names the file after "mcmc" for als too (the als switch rewrites -method, libfm.cpp:133)
-        rs.rmse_file = "test_rmse_" + nm.str() + "_" + (vb ? std::string("vb_online") : std::string("mcmc"));
-        rs.vb = vb;
-        rs.lfm = lfm;
-        rs.cls = cls;
-        rs.G = grouped || !rels.empty() ? ngroups : 1;
-        rs.k1 = dim[1] != 0;
-        rs.K = cfg.num_factor;
-        rs.ctx = ctx;
-        rs.test = &te;
-        rs.avg_collected = !lfm && (cfg.average == 1 || (cfg.average == 0 && cfg.quirks == SBMF_QUIRKS_NONE));  // sbmf.cpp avg_collected
-        if (general) {
-            rs.lo = *std::min_element(ctr.target, ctr.target + ctr.n);
-            rs.hi = *std::max_element(ctr.target, ctr.target + ctr.n);
-        } else if (lfm) {  // libFM clamps to the train target range (libfm.cpp:459-460)
-            rs.lo = *std::min_element(tr.rating, tr.rating + tr.n);
-            rs.hi = *std::max_element(tr.rating, tr.rating + tr.n);
-        } else {
-            rs.lo = cfg.clamp_lo >= 0 ? cfg.clamp_lo
-                                      : (cfg.quirks == SBMF_QUIRKS_SBPMF2 || cfg.quirks == SBMF_QUIRKS_BIAS2 ? 0.5 : 1.0);
-            rs.hi = cfg.clamp_hi;
-        }
-        { std::ofstream trunc(rs.rmse_file); }
-        std::ofstream rlog;
-        if (cl.has("rlog") && !cl.get("rlog", "").empty()) {
-            rlog.open(cl.get("rlog", ""));
-            if (!rlog.is_open()) throw std::runtime_error("Unable to open file " + cl.get("rlog", ""));
-            std::cout << "logging to " << cl.get("rlog", "") << std::endl;
-            rlog_header(rlog, rs);
-            rs.rlog = &rlog;
-        }
-        rs.verbosity = (int)cl.getl("verbosity", 0);
-        if (rec) chk(sbmf_watch_users(ctx, (uint32_t)rec_ids.size(), rec_ids.data(), 0));
-        if (recg)
-            chk(sbmf_foldin_users(ctx, (uint32_t)g_ptr.size() - 1, g_ptr.data(), g_items.data(), g_ratings.data(), 0));
-        if (recq) {
-            std::vector<const uint32_t*> rp(rel_stems.size(), nullptr);
-            for (size_t r = 0; r < rel_stems.size(); ++r)
-                if (r != rec_rel) rp[r] = q_rows[r].data();
-            chk(sbmf_fm_query_cases(ctx, (uint32_t)rec_rel, &qcases, rp.data(), q_erows.empty() ? nullptr : q_eptr.data(),
-                                    q_erows.empty() ? nullptr : q_erows.data(), 0));
-        }
-        chk(sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
-        if (recq) {
-            const size_t nq = qcases.n, topn = (size_t)rec_topn, slots = nq * topn;
-            std::vector<uint32_t> it(slots);
-            std::vector<double> mean(slots), sd(slots);
-            chk(sbmf_fm_query_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
-            FILE* f = std::fopen(cl.get("recommend_queries", "").c_str(), "w");
-            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend_queries", ""));
-            for (size_t g = 0; g < nq; ++g)
-                for (size_t k = 0; k < topn; ++k) {
-                    const size_t x = g * topn + k;
-                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
-                    std::fprintf(f, "%zu\t%u\t%.17g\t%.17g\n", g, it[x], mean[x], sd[x]);
-                }
-            std::fclose(f);
-        }
-        if (rec) {
-            const size_t topn = (size_t)rec_topn, slots = rec_ids.size() * topn;
-            std::vector<uint32_t> it(slots);
-            std::vector<double> mean(slots), sd(slots);
-            chk(sbmf_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
-            FILE* f = std::fopen(cl.get("recommend", "").c_str(), "w");
-            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend", ""));
-            // ids as in the input files: on libFM input the item's feature id
-            const uint64_t ioff = libfm_input ? off : 0;
-            for (size_t w = 0; w < rec_ids.size(); ++w)
-                for (size_t k = 0; k < topn; ++k) {
-                    const size_t x = w * topn + k;
-                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
-                    std::fprintf(f, "%u\t%llu\t%.17g\t%.17g\n", rec_ids[w], (unsigned long long)(it[x] + ioff), mean[x],
-                                 sd[x]);
-                }
-            std::fclose(f);
-        }
-        if (recg) {
-            const size_t ng = g_ptr.size() - 1, topn = (size_t)rec_topn, slots = ng * topn;
-            std::vector<uint32_t> it(slots);
-            std::vector<double> mean(slots), sd(slots);
-            chk(sbmf_foldin_recommend(ctx, (uint32_t)topn, 0, cl.getd("rec_risk", 0.0), it.data(), mean.data(), sd.data()));
-            FILE* f = std::fopen(cl.get("recommend_guests", "").c_str(), "w");
-            if (!f) throw std::runtime_error("Unable to open file " + cl.get("recommend_guests", ""));
-            const uint64_t ioff = libfm_input ? off : 0;
-            for (size_t g = 0; g < ng; ++g)
-                for (size_t k = 0; k < topn; ++k) {
-                    const size_t x = g * topn + k;
-                    if (it[x] == 0xffffffffu) continue;  // fewer candidates than topn
-                    std::fprintf(f, "%zu\t%llu\t%.17g\t%.17g\n", g, (unsigned long long)(it[x] + ioff), mean[x], sd[x]);
-                }
-            std::fclose(f);
-        }
-        if (cl.has("out") && !cl.get("out", "").empty()) {
-            std::vector<double> pred(nte);
-            chk(sbmf_predict(ctx, pred.data()));
-            std::ofstream out(cl.get("out", ""));
-            for (double p : pred) out << p << "\n";
-        }
+        Options o = resolve(cl);
+        HostData d;
+        load_data(o, d);
+        load_lists(o, d);
+        sbmf_ctx* ctx = create_context(o, d);
+        print_dims(ctx, o, d);
+        run(ctx, o, d);
+        write_outputs(ctx, o, d);
         sbmf_destroy(ctx);
-        if (general) te = sbmf_ratings{};  // its targets were te_y's
-        sbmf_free_ratings(&tr);
-        sbmf_free_ratings(&te);
-        sbmf_free_cases(&ctr);
-        sbmf_free_cases(&cte);
-        sbmf_free_cases(&qcases);
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return leave(1);
