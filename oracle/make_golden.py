@@ -20,7 +20,8 @@ Fixtures written (all data, no reference source):
   ref_rng_s<seed>.txt                         rand / ran_gaussian / ran_gamma
   ref_vbo_<data>_k<K>_s<seed>_e<E>.txt        E lines "%.17g" per-epoch test RMSE of the
                                               online VB learner (oracle/ref_vbo_harness.cpp
-                                              over the reference's fm_learn_vb_online*.h)
+                                              over the reference's fm_learn_vb_online*.h);
+                                              data vbedge: the set tests/vb_edge.py generates
   ref_libfm_<method>_<data>_d<k0><k1><K>_s<seed>_i<N>.txt
                                               libFM's stdout "#Iter=..." lines of bin/libFM -method
                                               mcmc|als (libfm.cpp compiled unmodified, time() pinned
@@ -145,7 +146,14 @@ def max_user(*paths):
     return m
 
 
-VBO_RUNS = [("ml100k", 8, 1, 10), ("ml100k", 20, 7, 5), ("ragged", 8, 2, 20)]
+VBO_RUNS = [("ml100k", 8, 1, 10), ("ml100k", 20, 7, 5), ("ragged", 8, 2, 20), ("vbedge", 8, 3, 3)]
+
+
+def write_libfm_arrays(path, triples, num_users):
+    """(user, item, rating) arrays -> the same users-first libFM text."""
+    with open(path, "w") as g:
+        for u, i, r in zip(*(a.tolist() for a in triples)):
+            g.write("%g %d:1 %d:1\n" % (r, u, num_users + i))
 
 
 def vbo_goldens():
@@ -154,10 +162,17 @@ def vbo_goldens():
     sets = {"ml100k": (os.path.join(GOLD, "ml100k_train.tsv.gz"), os.path.join(GOLD, "ml100k_test.tsv.gz")),
             "ragged": (os.path.join(GOLD, "ragged_train.tsv"), os.path.join(GOLD, "ragged_test.tsv"))}
     for dname, K, seed, epochs in VBO_RUNS:
-        tr, te = sets[dname]
-        I = max_user(tr, te) + 1
-        write_libfm(tr, os.path.join(root, "train.libfm"), I)
-        write_libfm(te, os.path.join(root, "test.libfm"), I)
+        if dname == "vbedge":  # the row-class edge set: tests/vb_edge.py is the data, no file is stored
+            sys.path.insert(0, os.path.join(REPO, "tests"))
+            import vb_edge
+            etr, ete, (I, _) = vb_edge.generate()
+            write_libfm_arrays(os.path.join(root, "train.libfm"), etr, I)
+            write_libfm_arrays(os.path.join(root, "test.libfm"), ete, I)
+        else:
+            tr, te = sets[dname]
+            I = max_user(tr, te) + 1
+            write_libfm(tr, os.path.join(root, "train.libfm"), I)
+            write_libfm(te, os.path.join(root, "test.libfm"), I)
         p = subprocess.run([os.path.join(HERE, "_ref", "ref_vbo_harness"), "train.libfm", "test.libfm", str(K),
                             str(epochs), str(seed), os.path.join(root, "scratch")], cwd=root, capture_output=True,
                            text=True, check=True)

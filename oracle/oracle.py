@@ -138,13 +138,15 @@ def run(train, test, K=20, iters=100, seed=1, quirks="final", burnin=0, num_user
             "num_items": res.num_items, "bu": bu, "bv": bv, "b0": res.b0}
 
 
-def run_vbo(train, test, K=8, epochs=10, seed=1, num_users=0, num_items=0, seconds_limit=0.0, want_params=True):
+def run_vbo(train, test, K=8, epochs=10, seed=1, num_users=0, num_items=0, seconds_limit=0.0, want_params=True,
+            num_batch=0):
     """The online VB oracle (vbo_oracle.c, the reference's -method vb_online on
-    rating data).  Returns per-epoch test 'rmse', final clamped 'pred', the
-    attribute means 'mu_w' [p] and 'mu_v' [p][K] (users first, then items),
-    'alpha', 'mu0', 'seconds'."""
+    rating data).  num_batch: mini-batches per epoch (0 = the reference's 30).
+    Returns per-epoch test 'rmse', final clamped 'pred', the attribute means
+    'mu_w' [p] and 'mu_v' [p][K] (users first, then items), 'alpha', 'mu0',
+    'seconds'."""
     L = lib()
-    cfg = VBOConfig(K, epochs, seed, 0, seconds_limit)
+    cfg = VBOConfig(K, epochs, seed, num_batch, seconds_limit)
     tu, ti, tr = (np.ascontiguousarray(train[0], np.uint32), np.ascontiguousarray(train[1], np.uint32),
                   np.ascontiguousarray(train[2], np.float64))
     su, si, sr = (np.ascontiguousarray(test[0], np.uint32), np.ascontiguousarray(test[1], np.uint32),
@@ -165,7 +167,7 @@ def run_vbo(train, test, K=8, epochs=10, seed=1, num_users=0, num_items=0, secon
                           _p(tr, C.c_double), C.c_uint64(len(sr)), _p(su, C.c_uint32), _p(si, C.c_uint32),
                           _p(sr, C.c_double), C.c_uint32(I), C.c_uint32(J), C.byref(res))
     if rc != 0:
-        raise ValueError("oracle_vbo_run failed (an empty batch: fewer ratings than the 30 batches need)")
+        raise ValueError("oracle_vbo_run failed (an empty batch: fewer ratings than the %d batches need)" % (num_batch or 30))
     n = res.epochs_done
     return {"rmse": rm[:n], "pred": pred[:len(sr)], "mu_w": mu_w, "mu_v": mu_v, "alpha": res.alpha, "mu0": res.mu0,
             "seconds": res.seconds, "epochs": n, "num_attribute": res.num_attribute}

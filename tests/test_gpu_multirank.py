@@ -99,23 +99,36 @@ def test_pipelined_ranks_match_single_rank(ml100k, tmp_path, nranks, quirks):
         assert np.array_equal(z["rmse"], rmse1)
 
 
-@pytest.mark.parametrize("nranks,data,K,seed,epochs,rng", [(2, "ml100k", 8, 1, 10, "ref"), (3, "ml100k", 20, 7, 5, "ref"),
-                                                           (3, "ragged", 8, 2, 20, "ref"), (2, "ml100k", 8, 5, 4, "philox")])
-def test_vb_ranks_on_one_gpu(ml100k, ragged, tmp_path, nranks, data, K, seed, epochs, rng):
+# the rows from before vb_batches keep their ids; data "vbedge" is the row-class edge set of
+# tests/vb_edge.py (VB_PART with item rows that loop on a rank, and items absent from a rank)
+@pytest.mark.parametrize("nranks,data,K,seed,epochs,rng,vb_batches", [
+    pytest.param(2, "ml100k", 8, 1, 10, "ref", 0, id="2-ml100k-8-1-10-ref"),
+    pytest.param(3, "ml100k", 20, 7, 5, "ref", 0, id="3-ml100k-20-7-5-ref"),
+    pytest.param(3, "ragged", 8, 2, 20, "ref", 0, id="3-ragged-8-2-20-ref"),
+    pytest.param(2, "ml100k", 8, 5, 4, "philox", 0, id="2-ml100k-8-5-4-philox"),
+    pytest.param(2, "vbedge", 8, 3, 2, "ref", 1, id="2-vbedge-8-3-2-ref-nb1"),
+    pytest.param(3, "vbedge", 8, 3, 2, "ref", 3, id="3-vbedge-8-3-2-ref-nb3")])
+def test_vb_ranks_on_one_gpu(ml100k, ragged, tmp_path, nranks, data, K, seed, epochs, rng, vb_batches):
     """Online VB over several ranks (users split into ranges, the item rows'
     sums all-gathered and added in rank order): every rank ends with the same
     means, the per-epoch test RMSE tracks the reference learner (golden, 1e-9,
-    as one rank does) and one rank's run to rounding (item sums added rank by
-    rank instead of in one group reduction)."""
-    tr, te = ml100k if data == "ml100k" else ragged
-    L = FMLearnVBOnline(num_factor=K, seed=seed, rng=rng)
-    L.set_data(Data(*tr), Data(*te))
+    as one rank does; the edge set at 1 / 3 batches: the oracle at that batch
+    count) and one rank's run to rounding (item sums added rank by rank instead
+    of in one group reduction)."""
+    dims = (0, 0)
+    if data == "vbedge":
+        import vb_edge
+        tr, te, dims = vb_edge.generate()
+    else:
+        tr, te = ml100k if data == "ml100k" else ragged
+    L = FMLearnVBOnline(num_factor=K, seed=seed, rng=rng, vb_batches=vb_batches)
+    L.set_data(Data(*tr), Data(*te), num_users=dims[0], num_items=dims[1])
     L.learn(sweeps=epochs)
     U1, V1 = L.factors()
     bu1, bv1, b01 = L.biases()
     rmse1, pred1 = L.rmse_trajectory, L.predict()
     L.close()
-    outs = _run_ranks(tmp_path, nranks, [str(K), str(epochs), str(seed), rng, "0", "final", "vb"],
+    outs = _run_ranks(tmp_path, nranks, [str(K), str(epochs), str(seed), rng, "0", "final", "vb", str(vb_batches)],
                       env={"SBMF_WORKER_DATA": data})
     z0 = np.load(outs[0])
     for r in range(1, nranks):  # identical on every rank
@@ -129,7 +142,12 @@ def test_vb_ranks_on_one_gpu(ml100k, ragged, tmp_path, nranks, data, K, seed, ep
     assert np.abs(z0["bu"] - bu1).max() < 1e-9 and np.abs(z0["bv"] - bv1).max() < 1e-9
     assert abs(z0["b0"][0] - b01) < 1e-11
     assert np.abs(z0["pred"] - pred1).max() < 1e-9
-    if rng == "ref":
+    if data == "vbedge":
+        import oracle
+        gold = oracle.run_vbo(tr, te, K=K, epochs=epochs, seed=seed, num_users=dims[0], num_items=dims[1],
+                              num_batch=vb_batches)["rmse"]
+        assert np.abs(z0["rmse"] - gold).max() < 1e-9
+    elif rng == "ref":
         gold = golden_rmse("ref_vbo_%s_k%d_s%d_e%d.txt" % (data, K, seed, epochs))
         assert np.abs(z0["rmse"] - gold).max() < 1e-9
 

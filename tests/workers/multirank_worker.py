@@ -1,10 +1,13 @@
 """One rank of the multi-rank sampler (spawned by tests/test_gpu_multirank.py).
 
 usage: python multirank_worker.py <rank> <nranks> <id-hex> <out.npz> <K> <sweeps> <seed> <rng> [tune] [quirks] [method]
+       [vb_batches]
 The ranks share one GPU and exchange their row blocks through the host comm
 backend (the id was made with SBMF_COMM=host); the result must equal a
 single-rank run in the same residual form.  method "vb": the online VB
-learner (user ranges per rank, item sums all-gathered), `sweeps` epochs.
+learner (user ranges per rank, item sums all-gathered), `sweeps` epochs of
+`vb_batches` mini-batches (0: the reference's 30).  SBMF_WORKER_DATA=vbedge:
+the row-class edge set of tests/vb_edge.py.
 """
 import gzip
 import os
@@ -35,6 +38,7 @@ def main():
     tune = int(sys.argv[9]) if len(sys.argv) > 9 else 0
     quirks = sys.argv[10] if len(sys.argv) > 10 else "final"
     method = sys.argv[11] if len(sys.argv) > 11 else "mcmc"
+    vb_batches = int(sys.argv[12]) if len(sys.argv) > 12 else 0
     from sbmf import Data, FMLearnSBPMF, FMLearnVBOnline
     g = os.path.join(REPO, "tests", "golden")
     data = os.environ.get("SBMF_WORKER_DATA", "ml100k")
@@ -44,10 +48,14 @@ def main():
         tr, te, dims = synth.generate(data[6:])
         if os.environ.get("SBMF_WORKER_RELABEL") == "degree":
             tr, te, dims = synth.relabel_by_degree(tr, te, dims)
+    elif data == "vbedge":
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import vb_edge
+        tr, te, dims = vb_edge.generate()
     else:
         tr, te = read(os.path.join(g, data + "_train.tsv.gz")), read(os.path.join(g, data + "_test.tsv.gz"))
     if method == "vb":
-        L = FMLearnVBOnline(num_factor=int(K), seed=int(seed), rng=rng, device=0)
+        L = FMLearnVBOnline(num_factor=int(K), seed=int(seed), rng=rng, device=0, vb_batches=vb_batches)
     elif method in ("libfm", "als"):  # libFM's own chain: quirks carries "k0,k1;regular"
         dim, reg = quirks.split(";")
         k0, k1 = (int(x) for x in dim.split(","))
