@@ -420,6 +420,87 @@ int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double r
  * the first. */
 int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select);
 
+/* --- posterior sample store: top-N and pair predictions for any user after the run ----------- */
+/* Not a reference interface.  The lists above are named before the first
+ * collected sweep and their sums live in the process; a sample store keeps
+ * thinned samples of the chain itself -- U, V and, with the biased quirk sets,
+ * b0, b_u, b_j -- on the device, so that the chain can be used after it ends:
+ * top-N for users chosen later, mean and spread of arbitrary pairs, both also
+ * from a file in a later process.  One sample takes (I + J) Kp elements of the
+ * context's precision (Kp = K rounded up to 16) plus, with biases, (I + J)
+ * doubles: ML-20M K = 100 f64 is 148 MB a sample.  The chain is untouched: a
+ * context with a store draws bit for bit what it draws without one, and
+ * sbmf_set_factors leaves the store alone.
+ * Scope: the SBPMF sampler (SBMF_METHOD_MCMC), every quirk set, both
+ * precisions, both RNG modes, one rank.  SBMF_E_STATE with a message naming
+ * the reason: the VB, libFM-MCMC and ALS learners; a context that joined a
+ * communicator; a virtual rank; reading before a sample is kept ("no sample
+ * kept yet").
+ *
+ * sbmf_keep_samples: register (or replace) the store.  After sbmf_prepare,
+ * also between sbmf_run calls.  Allocates cap slots up front (a failure is
+ * SBMF_E_NOMEM with the byte count in the message; the store is then dropped).
+ * The collected sweeps are counted from registration, starting at 0, and
+ * every sweep whose count is a multiple of `every` is copied into the next
+ * slot -- the first collected sweep after registration is kept; burn-in
+ * sweeps never are.  A full store overwrites its oldest sample.  cap = 0
+ * drops the store; every = 0 or cap > 65535 is SBMF_E_ARG. */
+int sbmf_keep_samples(sbmf_ctx* ctx, uint32_t every, uint32_t cap);
+/* The store's state: samples kept, slots, the thinning and the device bytes of
+ * the slots (all 0, every 1, without a store).  Any pointer may be NULL. */
+int sbmf_samples_info(sbmf_ctx* ctx, uint32_t* count, uint32_t* cap, uint32_t* every, uint64_t* bytes);
+/* Sample s, 0 the oldest kept: its absolute sweep index, U [I][K], V [J][K] as
+ * doubles (an F32 store widens exactly), bu [I], bv [J], b0 (zeros without
+ * biases).  Any output pointer may be NULL.  s >= count is SBMF_E_ARG. */
+int sbmf_get_sample(sbmf_ctx* ctx, uint32_t s, uint32_t* sweep, double* U, double* V, double* bu, double* bv,
+                    double* b0);
+/* sbmf_recommend for any n users, named now: per user the topn (1..1024) items
+ * with the largest key mean - risk * stdev over the stored samples, the key,
+ * order, tie rule, outputs [n][topn] and empty slots as there.  The score of
+ * (user, j) at sample s is U_s[user] . V_s[j] (+ (b0_s + bu_s[user]) + bv_s[j]
+ * with biases), its sums run over the samples oldest first in f64, in a fixed
+ * order without atomics (a rerun is bit-identical; a watch list registered
+ * before the first kept sweep of an every = 1 store adds the same products in
+ * the same order).  flags bit 0: keep the items the user rated in training;
+ * bit 1: clamp each sample's score to [clamp_lo, clamp_hi].  Ids may repeat.
+ * The temporary [n][Jp] sums are allocated for the call and freed after it;
+ * the users are processed in slices whose two sums stay within 1 GiB (whole
+ * groups of 64 users, one group at least).  stdev may be NULL; with one
+ * sample it is exactly 0. */
+int sbmf_samples_recommend(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t topn, uint32_t flags, double risk,
+                           uint32_t* items, double* mean, double* stdev);
+/* One user's full row, mean[j] and stdev[j] for j < num_items: exactly the
+ * values sbmf_samples_recommend ranks by.  flags bit 1: clamp. */
+int sbmf_samples_scores(sbmf_ctx* ctx, uint32_t user, uint32_t flags, double* mean, double* stdev);
+/* Posterior mean and population stdev of n arbitrary pairs (users[p],
+ * items[p]) over the stored samples, oldest first, dots in f64 in a fixed
+ * order.  flags bit 1: clamp.  An id out of range is SBMF_E_ARG.  stdev may
+ * be NULL. */
+int sbmf_samples_predict(sbmf_ctx* ctx, uint64_t n, const uint32_t* users, const uint32_t* items, uint32_t flags,
+                         double* mean, double* stdev);
+/* Device time (HIP events), ms: the last kept sweep's copy into the store, the
+ * last scoring launch of sbmf_samples_recommend / sbmf_samples_scores (its
+ * last slice) and the last selection; 0 before the first. */
+int sbmf_samples_timing(sbmf_ctx* ctx, double* ms_copy, double* ms_score, double* ms_select);
+/* The store to and from one little-endian file (the format: INTEGRATION.md
+ * 3d).  Loading needs a prepared context of the file's num_users, num_items,
+ * K, precision and bias-ness (else SBMF_E_ARG naming the field and both
+ * values); it replaces the store's samples (cap grows to the file's count if
+ * it was smaller, a context without a store gets one of that cap) and does
+ * not touch the chain: a context may be created, given its train set (for the
+ * rated-item mask), prepared, loaded and queried without one sweep.  File
+ * errors are SBMF_E_IO. */
+int sbmf_save_samples(sbmf_ctx* ctx, const char* path);
+int sbmf_load_samples(sbmf_ctx* ctx, const char* path);
+/* Reads and validates a sample file's header alone (no context, no GPU) and
+ * reports its fields and the file's size in bytes; any pointer but path may
+ * be NULL.  SBMF_E_IO with a message (sbmf_last_global_error) for a file that
+ * cannot be opened, a bad magic, an unknown version, a bad field, and a file
+ * shorter ("truncated in its header" / "in its body") or longer ("trailing
+ * bytes") than its header implies. */
+int sbmf_samples_file_info(const char* path, uint32_t* version, uint32_t* precision, uint32_t* num_users,
+                           uint32_t* num_items, uint32_t* num_factor, uint32_t* count, uint32_t* bias, uint64_t* bytes);
+
 /* --- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------------------- */
 /* 128-byte RCCL unique id, produced by rank 0 and shared by the launcher. */
 int sbmf_comm_unique_id(uint8_t id[128]);
@@ -806,6 +887,12 @@ int sbmf_test_tgauss(int mode, int device, uint64_t seed, uint32_t it, uint64_t 
 /* The shape the lists' scoring launch takes for factor rows of Kp values (needs no GPU): the
  * rows of the list one workgroup holds in LDS, and the bytes of dynamic LDS it asks for. */
 int sbmf_test_watch_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
+/* The same for the sample store's scoring launch (a sample's user rows, their biases and ids). */
+int sbmf_test_samples_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
+/* The sample store's scoring, for tests and measurements: budget_bytes replaces the 1 GiB of
+ * sbmf_samples_recommend's temporaries (0: the default); unfused != 0 scores with one launch of the
+ * watch list's kernel per stored sample into sums in memory in place of the fused kernel. */
+int sbmf_test_samples_tune(sbmf_ctx* ctx, uint64_t budget_bytes, int unfused);
 
 #ifdef __cplusplus
 }

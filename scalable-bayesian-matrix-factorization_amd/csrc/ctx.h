@@ -29,6 +29,7 @@
 #include "fmq.h"
 #include "foldin.h"
 #include "recommend.h"
+#include "samples.h"
 #include "vbo.h"
 
 struct sbmf_ctx;
@@ -119,6 +120,31 @@ struct ScoreList {
     void scores(sbmf_ctx* c, const char* fn, uint32_t row, double* mean, double* stdev);
     void recommend(sbmf_ctx* c, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn, uint32_t flags,
                    double risk, uint32_t* items, double* mean, double* stdev);
+};
+
+// The posterior sample store (sbmf_keep_samples, samples.cpp): a ring of `cap` slots on the device,
+// each a copy of U [I][Kp] and V [J][Kp] in the context's precision and, with the biased sampler,
+// of bu [I] and bv [J]; b0 and the sweep index of every slot stay on the host.  The oldest sample
+// is in slot `head`; every `every`-th collected sweep since registration is kept (`seen` counts
+// them), the newest overwriting the oldest once the ring is full.  Nothing here exists while
+// no store is registered (cap == 0).
+struct SampleStore {
+    uint32_t cap = 0, every = 1, head = 0, count = 0, seen = 0;
+    size_t bytes = 0;  // device bytes of the slots
+    DBuf d_U, d_V, d_bu, d_bv;
+    std::vector<double> b0;       // [cap], by slot
+    std::vector<uint32_t> sweep;  // [cap], by slot
+    hipEvent_t cev[2] = {}, scv[2] = {}, sel[2] = {};  // the last copy, scoring and selection [begin, end]
+    bool timed_copy = false, timed_score = false, timed_select = false;
+    // test hook (sbmf_test_samples_tune): the temporaries' budget in bytes (0: the default) and
+    // the per-sample loop of launch_watch_accum in the fused kernel's place
+    uint64_t budget = 0;
+    bool unfused = false;
+    uint32_t slot(uint32_t s) const { return (head + s) % cap; }  // of the s-th oldest sample
+    void alloc(sbmf_ctx* c, uint32_t cap_, uint32_t every_);
+    void drop();
+    template <typename T>
+    void keep(sbmf_ctx* c, double b0_, hipStream_t se);  // this sweep's tables into the next slot, if it is one to keep
 };
 
 struct sbmf_ctx {
@@ -263,6 +289,7 @@ struct sbmf_ctx {
     // points at it while a list is registered).  Nothing here exists while no list is registered.
     ScoreList fmq{"query list", "sbmf_fm_query_cases"};
     FMQueryList fmqd;
+    SampleStore samples;
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
     // -method mcmc --order libfm / als: libFM's chain (fmc.cpp) on triples (fmm.cpp) or on cases
     // with any number of features (fmg.cpp).  ctr / cte: the host copies of sbmf_set_train_cases /

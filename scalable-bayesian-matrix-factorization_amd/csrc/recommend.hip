@@ -8,24 +8,10 @@
 
 #include <cmath>
 
+#include "recommend_dev.h"
 #include "rng.h"
 
 namespace sbmf {
-
-typedef double wd4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ void load4(const T* p, double (&b)[4]);
-template <>
-__device__ __forceinline__ void load4<double>(const double* p, double (&b)[4]) {
-    const double2 x = *reinterpret_cast<const double2*>(p), y = *reinterpret_cast<const double2*>(p + 2);
-    b[0] = x.x, b[1] = x.y, b[2] = y.x, b[3] = y.y;
-}
-template <>
-__device__ __forceinline__ void load4<float>(const float* p, double (&b)[4]) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    b[0] = (double)x.x, b[1] = (double)x.y, b[2] = (double)x.z, b[3] = (double)x.w;
-}
 
 // ------------------------------------------------------------------ accumulation
 // A workgroup of four waves takes 16 MU watched users and WATCH_TILES item tiles of 16.  It
@@ -87,18 +73,7 @@ __global__ __launch_bounds__(256) void k_watch_accum(const uint32_t* __restrict_
                     o2[t][j] = ok ? S2[o] : 0.0;
                 }
         }
-        for (uint32_t k0 = 0; k0 < Kp; k0 += 16) {
-            double b[4];
-            load4<T>(vp + k0, b);
-#pragma unroll
-            for (int t = 0; t < MU; ++t) {
-                if (w0 + t * 16 >= n) continue;  // a tile past the list (uniform)
-                double a[4];
-                load4<double>(us + (size_t)(t * 16 + n16) * ld + k0 + 4 * kq, a);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc[t], 0, 0, 0);
-            }
-        }
+        watch_tile_products<T, MU>(us, ld, vp, Kp, w0, n, n16, kq, acc);
         if (item >= J) continue;
         const double bj = bu ? bv[item] : 0.0;
 #pragma unroll
@@ -107,20 +82,15 @@ __global__ __launch_bounds__(256) void k_watch_accum(const uint32_t* __restrict_
             for (int j = 0; j < 4; ++j) {
                 const uint32_t r = t * 16 + kq + 4 * j, w = w0 + r;
                 if (w >= n) continue;
-                double s = acc[t][j];
-                if (bu) s = ((b0 + bu[uid[r]]) + bj) + s;  // as k_test adds them
+                double s = watch_biased(acc[t][j], bu != nullptr, b0, bu ? bu[uid[r]] : 0.0, bj);
                 if constexpr (EPI & WATCH_EPI_CDF) s = ref_cdf_gaussian(s);
-                if (clamp) {
-                    s = (s < hi) ? s : hi;
-                    s = (lo < s) ? s : lo;
-                }
+                s = watch_clamped(s, clamp, lo, hi);
                 const size_t o = (size_t)w * Jp + item;
                 if constexpr (EPI & WATCH_EPI_SET) {
                     S1[o] = s;
                     S2[o] = s * s;
                 } else {
-                    S1[o] = o1[t][j] + s;
-                    S2[o] = o2[t][j] + s * s;
+                    watch_sums_add(o1[t][j], o2[t][j], s, S1[o], S2[o]);
                 }
             }
     }
@@ -185,16 +155,7 @@ hipError_t launch_watch_accum_epi(int epi, const uint32_t* rows, uint32_t n, con
 }
 
 // ------------------------------------------------------------------ moments and keys
-// One place for the expressions, without contraction: sbmf_watch_scores returns exactly the
-// mean and stdev the selection ranks by, and a caller forming mean - risk * stdev from them in
-// IEEE double arithmetic gets the selection's key bit for bit.
-__device__ __forceinline__ void watch_moments(double s1, double s2, double nw, double& mean, double& sd) {
-#pragma clang fp contract(off)
-    mean = s1 / nw;
-    const double mm = mean * mean;
-    const double v = s2 / nw - mm;
-    sd = sqrt(v > 0.0 ? v : 0.0);
-}
+// (watch_moments, the one place for the mean / stdev expressions: recommend_dev.h)
 // The key as an unsigned integer of the same order (a larger key is a larger integer); -0 as +0.
 __device__ __forceinline__ uint64_t watch_key(double mean, double sd, double risk) {
 #pragma clang fp contract(off)

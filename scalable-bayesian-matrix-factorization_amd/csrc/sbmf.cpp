@@ -48,6 +48,7 @@ sbmf_ctx::~sbmf_ctx() {
     for (hipEvent_t& e : fev) event_destroy(e);
     for (ScoreList* l : {&watch, &guests, &fmq}) l->drop();
     fmqd.drop();
+    samples.drop();
     pinned_free(h_fhyp, h_fhyp_bytes);
     event_destroy(hev);
     stream_destroy(sto);

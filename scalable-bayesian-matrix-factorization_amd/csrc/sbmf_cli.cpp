@@ -21,6 +21,9 @@
 // their ratings (sbmf_foldin_users / sbmf_foldin_recommend).  -recommend_queries / -rec_queries /
 // -rec_relation / -rec_exclude write, for libFM's MCMC / ALS learner with -relation, the posterior
 // top-N block rows of one relation for a list of query cases (sbmf_fm_query_cases).
+// -samples_out / -samples_every / -samples_max keep thinned samples of the SBPMF chain and write them to a
+// file after the run (sbmf_keep_samples / sbmf_save_samples); -samples_in runs no sweep: it loads such a
+// file and serves -out and -recommend from it (sbmf_load_samples / sbmf_samples_predict / sbmf_samples_recommend).
 // Differences, by design: -seed is honoured (libfm.cpp:124 ignores it); on
 // error the exit code is 1 (the reference prints "ERROR" and returns 0).
 #include <algorithm>
@@ -477,6 +480,18 @@ void register_flags(CmdLine& cl) {
                           "each query, one per line [MANDATORY with -recommend_queries]");
     cl.reg("rec_relation", "the relation whose block rows are ranked: one of -relation's stems [MANDATORY with "
                            "-recommend_queries]");
+    // the posterior sample store (sbmf_keep_samples / sbmf_save_samples / sbmf_load_samples)
+    cl.reg("samples_out", "filename for output: the kept posterior samples of the chain (U, V and the biases of "
+                          "every -samples_every-th collected sweep), written after the run; the SBPMF sampler only "
+                          "(-method mcmc -order sbpmf)");
+    cl.reg("samples_every", "keep every n-th collected sweep; default=1 [with -samples_out]");
+    cl.reg("samples_max", "keep the last m of them, 1..65535; default: every kept sweep of the run; the store is allocated "
+                          "on the device up front, m x (users + items) x K' x 8 bytes (4 with -precision f32; K' = K rounded up "
+                          "to 16; + (users + items) x 8 with biases) -- 148 MB a sample at ML-20M K=100 [with -samples_out]");
+    cl.reg("samples_in", "filename of a -samples_out file: no sweep is run; prints '#Samples=<count><TAB>Test=<rmse>' of "
+                         "the clamped posterior-mean prediction of the -test pairs, writes -out from it and, with "
+                         "-recommend / -rec_users, the top-N lists from the stored samples; the data, -dim, -precision "
+                         "and -quirks must be those of the run that wrote the file");
     cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
                           "numbers non-decreasing");
 }
@@ -493,6 +508,8 @@ struct Options {
     std::vector<int> dim;
     sbmf_config cfg;
     ListOpt users, guests, queries;
+    std::string samples_out, samples_in;  // the sample store: written after the run | served from, without one
+    long samples_every = 1, samples_max = 0;  // (0: every kept sweep of the run)
     long topn = 10;  // -rec_topn and -rec_risk, shared by the three
     double risk = 0.0;
     std::vector<std::string> rel_stems;  // -relation's stems, and which of them -rec_relation names
@@ -506,6 +523,7 @@ const char* const task_refusal = "only -task r (regression) is supported by the 
 const char* const rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
 const char* const recg_refusal = "-recommend_guests is offered by the SBPMF sampler (-method mcmc -order sbpmf) with "
                                  "the unbiased quirk sets (final, sbpmf2, none)";
+const char* const samples_refusal = "-samples_out / -samples_in are offered by the SBPMF sampler (-method mcmc -order sbpmf)";
 const char* const recq_refusal = "-recommend_queries is offered by libFM's MCMC / ALS learner (-method mcmc -order libfm, "
                                  "-method als) with -relation: it ranks the block rows of one relation";
 
@@ -559,6 +577,21 @@ void resolve_flags(const CmdLine& cl, Options& o) {
     o.exclude = cl.get("rec_exclude", "");
     o.fmt = cl.get("format", "auto");
     if (o.fmt != "auto" && o.fmt != "triple" && o.fmt != "libfm" && o.fmt != "binary") fail("unknown -format " + o.fmt);
+    // the sample store's flags, after every check above
+    o.samples_out = cl.get("samples_out", "");
+    o.samples_in = cl.get("samples_in", "");
+    if (cl.has("samples_out") && o.samples_out.empty()) fail("-samples_out needs a file name");
+    if (cl.has("samples_in") && o.samples_in.empty()) fail("-samples_in needs a file name");
+    if (!cl.has("samples_out") && (cl.has("samples_every") || cl.has("samples_max")))
+        fail("-samples_every / -samples_max go with -samples_out <file>");
+    if (cl.has("samples_in") && (cl.has("samples_out") || recg.on || cl.has("rlog")))
+        fail("-samples_in runs no sweep: it does not go with -samples_out, -recommend_guests or -rlog");
+    if ((cl.has("samples_out") || cl.has("samples_in")) && (o.method != "mcmc" || cl.get("order", "") == "libfm"))
+        fail(samples_refusal);
+    o.samples_every = cl.getl("samples_every", 1);
+    o.samples_max = cl.getl("samples_max", 0);
+    if (cl.has("samples_every") && o.samples_every < 1) fail("-samples_every must be at least 1");
+    if (cl.has("samples_max") && (o.samples_max < 1 || o.samples_max > 65535)) fail("-samples_max must be in 1..65535");
 }
 
 // Step 2: what also depends on the kind of input, for which -format auto looks into the train file (the first
@@ -589,6 +622,7 @@ void resolve_learner(const CmdLine& cl, Options& o) {
     if (o.users.on && o.lfm) fail(rec_refusal);
     if (o.queries.on && !o.lfm) fail(recq_refusal);
     if (o.guests.on && (o.lfm || o.biased)) fail(recg_refusal);  // (a guest bias would need its own draw)
+    if ((!o.samples_out.empty() || !o.samples_in.empty()) && o.lfm) fail(samples_refusal);
     if (o.method != "mcmc" && !o.vb && !o.als) fail("-method " + o.method + " is not supported (use mcmc, als or vb)");
     if (!cl.has("train") || !cl.has("test")) fail("-train and -test are mandatory");
     const std::vector<int>& dim = o.dim = split_ints(cl.get("dim", "1,1,8"));
@@ -910,12 +944,23 @@ void run(sbmf_ctx* ctx, const Options& o, const HostData& d) {
         chk(ctx, sbmf_fm_query_cases(ctx, (uint32_t)o.rec_rel, &d.qcases, rp.data(), none ? nullptr : d.excl.ptr.data(),
                                      none ? nullptr : d.excl.val.data(), 0));
     }
+    if (!o.samples_out.empty()) {
+        // the sweeps the run collects (the sbpmf2 quirk set collects its burn-in too), thinned
+        const uint64_t collected = (uint64_t)cfg.num_iter + (cfg.quirks == SBMF_QUIRKS_SBPMF2 ? cfg.burnin : 0);
+        const uint64_t kept = (collected + (uint64_t)o.samples_every - 1) / (uint64_t)o.samples_every;
+        if (!o.samples_max && kept > 65535)
+            fail("-samples_out: the run keeps " + std::to_string(kept) + " samples; a store holds 65535 at most (-samples_every, -samples_max)");
+        const uint64_t cap = o.samples_max ? std::min<uint64_t>((uint64_t)o.samples_max, std::max<uint64_t>(kept, 1)) : std::max<uint64_t>(kept, 1);
+        chk(ctx, sbmf_keep_samples(ctx, (uint32_t)std::min<long>(o.samples_every, 0xffffffffl), (uint32_t)cap));
+    }
     chk(ctx, sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
+    if (!o.samples_out.empty()) chk(ctx, sbmf_save_samples(ctx, o.samples_out.c_str()));
 }
 
 // One top-N file: `recommend` fills topn slots per row of its list; every filled slot is a line
 // "row<TAB>item<TAB>mean<TAB>stdev", the row as its id (`ids`) or else its number, the item moved by ioff
-using Recommend = int (*)(sbmf_ctx*, uint32_t, uint32_t, double, uint32_t*, double*, double*);
+// (`recommend`: one of the lists' sbmf_*_recommend, or a callable of that shape)
+template <class Recommend>
 void write_topn(sbmf_ctx* ctx, Recommend recommend, const Options& o, const std::string& path, size_t rows,
                 const uint32_t* ids, uint64_t ioff) {
     const size_t topn = (size_t)o.topn, slots = rows * topn;
@@ -944,6 +989,32 @@ void write_outputs(sbmf_ctx* ctx, const Options& o, const HostData& d) {
         chk(ctx, sbmf_get_dims(ctx, nullptr, nullptr, nullptr, &nte));
         std::vector<double> pred(nte);
         chk(ctx, sbmf_predict(ctx, pred.data()));
+        std::ofstream out(o.out);
+        for (double p : pred) out << p << "\n";
+    }
+}
+
+// -samples_in: no sweep.  The stored samples' clamped posterior-mean prediction of the test pairs, its RMSE on
+// the "#Samples=" line, -out from it, and -recommend's lists from the store through the top-N writer.
+void serve_samples(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    chk(ctx, sbmf_load_samples(ctx, o.samples_in.c_str()));
+    uint32_t count = 0;
+    chk(ctx, sbmf_samples_info(ctx, &count, nullptr, nullptr, nullptr));
+    const uint64_t n = d.te.n;
+    std::vector<double> pred(n);
+    chk(ctx, sbmf_samples_predict(ctx, n, d.te.user, d.te.item, 2u, pred.data(), nullptr));
+    double se = 0.0;
+    for (uint64_t t = 0; t < n; ++t) se += (pred[t] - d.te.rating[t]) * (pred[t] - d.te.rating[t]);
+    std::cout << "#Samples=" << count << "\tTest=" << (n ? std::sqrt(se / (double)n) : std::numeric_limits<double>::quiet_NaN())
+              << std::endl;
+    if (o.users.on) {
+        const uint32_t nu = (uint32_t)d.rec_ids.size();
+        const uint32_t* ids = d.rec_ids.data();
+        write_topn(ctx, [&](sbmf_ctx* c, uint32_t topn, uint32_t flags, double risk, uint32_t* it, double* mean, double* sd) {
+            return sbmf_samples_recommend(c, nu, ids, topn, flags, risk, it, mean, sd);
+        }, o, o.users.out, d.rec_ids.size(), ids, d.ioff);
+    }
+    if (!o.out.empty()) {
         std::ofstream out(o.out);
         for (double p : pred) out << p << "\n";
     }
@@ -985,8 +1056,12 @@ int main(int argc, char** argv) {
         load_lists(o, d);
         sbmf_ctx* ctx = create_context(o, d);
         print_dims(ctx, o, d);
-        run(ctx, o, d);
-        write_outputs(ctx, o, d);
+        if (!o.samples_in.empty()) {
+            serve_samples(ctx, o, d);
+        } else {
+            run(ctx, o, d);
+            write_outputs(ctx, o, d);
+        }
         sbmf_destroy(ctx);
     } catch (const std::exception& e) {
         std::cerr << "ERROR: " << e.what() << std::endl;

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "samples_file_info", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -653,6 +653,76 @@ class FMLearnSBPMF:
         self._check(lib.sbmf_watch_timing(self.ctx, C.byref(a), C.byref(b)))
         return {"ms_score": a.value, "ms_select": b.value}
 
+    # -- posterior sample store: thinned samples of the chain kept on the device, scored after the run
+    def keep_samples(self, every=1, cap=64):
+        """Keep every ``every``-th collected sweep from now on in a ring of ``cap`` samples
+        (sbmf_keep_samples); ``cap`` 0 drops the store and frees its device buffers."""
+        self._check(lib.sbmf_keep_samples(self.ctx, int(every), int(cap)))
+
+    def samples_info(self):
+        """{"count", "cap", "every", "bytes"} of the store."""
+        c, k, e, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(lib.sbmf_samples_info(self.ctx, C.byref(c), C.byref(k), C.byref(e), C.byref(b)))
+        return {"count": c.value, "cap": k.value, "every": e.value, "bytes": b.value}
+
+    def sample(self, s):
+        """Stored sample ``s`` (0 the oldest): {"sweep", "U" [users, K], "V" [items, K], "bu", "bv", "b0"}."""
+        nu, ni, _, _ = self.dims()
+        K = self.cfg.num_factor
+        U, V, bu, bv = np.zeros((nu, K)), np.zeros((ni, K)), np.zeros(nu), np.zeros(ni)
+        sw, b0 = C.c_uint32(), C.c_double()
+        self._check(lib.sbmf_get_sample(self.ctx, int(s), C.byref(sw), _ptr(U, C.c_double), _ptr(V, C.c_double),
+                                        _ptr(bu, C.c_double), _ptr(bv, C.c_double), C.byref(b0)))
+        return {"sweep": sw.value, "U": U, "V": V, "bu": bu, "bv": bv, "b0": b0.value}
+
+    def samples_scores(self, user, clamp=False):
+        """(mean, stdev) of ``user``'s score of every item over the stored samples."""
+        _, ni, _, _ = self.dims()
+        mean, sd = np.zeros(ni), np.zeros(ni)
+        self._check(lib.sbmf_samples_scores(self.ctx, int(user), 2 if clamp else 0, _ptr(mean, C.c_double),
+                                            _ptr(sd, C.c_double)))
+        return mean, sd
+
+    def samples_recommend(self, users, topn=10, exclude_rated=True, risk=0.0, clamp=False):
+        """``recommend`` for any users, named now, from the stored samples: (items int64
+        [n, topn] with -1 in empty slots, mean, stdev)."""
+        users = _u32(users).ravel()
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        n, t = len(users), int(topn)
+        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
+        flags = (0 if exclude_rated else 1) | (2 if clamp else 0)
+        self._check(lib.sbmf_samples_recommend(self.ctx, n, _ptr(users, C.c_uint32), t, flags, float(risk),
+                                               _ptr(items, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = items[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def samples_predict(self, users, items, clamp=False):
+        """(mean, stdev) of the pairs (users[p], items[p]) over the stored samples."""
+        users, items = _u32(users).ravel(), _u32(items).ravel()
+        if len(users) != len(items):
+            raise ValueError("users and items must have the same length")
+        mean, sd = np.zeros(len(users)), np.zeros(len(users))
+        self._check(lib.sbmf_samples_predict(self.ctx, len(users), _ptr(users, C.c_uint32), _ptr(items, C.c_uint32),
+                                             2 if clamp else 0, _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        return mean, sd
+
+    def samples_timing(self):
+        """Device ms of the last copy into the store, the last scoring launch and the last selection."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(lib.sbmf_samples_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"ms_copy": a.value, "ms_score": b.value, "ms_select": c.value}
+
+    def save_samples(self, path):
+        self._check(lib.sbmf_save_samples(self.ctx, str(path).encode()))
+
+    def load_samples(self, path):
+        """Replace the store by a sample file's (a prepared learner of the same dims, K,
+        precision and quirk-set bias-ness; no sweep needed)."""
+        self._check(lib.sbmf_load_samples(self.ctx, str(path).encode()))
+
     # -- posterior top-N for guests: users outside the training set, given by their ratings
     def foldin(self, guests, clamp=False):
         """Register a fold-in list (sbmf_foldin_users): ``guests`` is a list of
@@ -804,6 +874,22 @@ class FMLearnVBOnline(FMLearnSBPMF):
     def __init__(self, num_factor=8, num_iter=100, seed=1, rng="ref", device=0, vb_batches=0, **kw):
         super().__init__(num_factor=num_factor, num_iter=num_iter, seed=seed, rng=rng, device=device, method="vb",
                          vb_batches=vb_batches, **kw)
+
+
+def samples_file_info(path):
+    """sbmf_samples_file_info: a sample file's header, validated against the file's size (no GPU):
+    {"version", "precision" ("f64" | "f32"), "num_users", "num_items", "num_factor", "count", "bias", "bytes"}."""
+    v = [C.c_uint32() for _ in range(7)]
+    b = C.c_uint64()
+    rc = lib.sbmf_samples_file_info(str(path).encode(), *[C.byref(x) for x in v], C.byref(b))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    keys = ("version", "precision", "num_users", "num_items", "num_factor", "count", "bias")
+    out = {k: x.value for k, x in zip(keys, v)}
+    out["precision"] = "f32" if out["precision"] == F32 else "f64"
+    out["bias"] = bool(out["bias"])
+    out["bytes"] = b.value
+    return out
 
 
 def device_usage(device=0):

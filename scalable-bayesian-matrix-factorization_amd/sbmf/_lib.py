@@ -119,6 +119,18 @@ SIGNATURES = {
     "sbmf_foldin_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
     "sbmf_foldin_recommend": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
     "sbmf_foldin_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
+    "sbmf_keep_samples": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sbmf_samples_info": (C.c_int, [C.c_void_p, _P_U32, _P_U32, _P_U32, C.POINTER(C.c_uint64)]),
+    "sbmf_get_sample": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_F64, _P_F64, _P_F64, _P_F64, _P_F64]),
+    "sbmf_samples_recommend": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, C.c_uint32, C.c_uint32, C.c_double, _P_U32,
+                                         _P_F64, _P_F64]),
+    "sbmf_samples_scores": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_samples_predict": (C.c_int, [C.c_void_p, C.c_uint64, _P_U32, _P_U32, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_samples_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
+    "sbmf_save_samples": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_load_samples": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_samples_file_info": (C.c_int, [C.c_char_p, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32,
+                                         C.POINTER(C.c_uint64)]),
     "sbmf_fm_query_cases": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CasesC), C.POINTER(_P_U32), _P_U32, _P_U32,
                                       C.c_uint32]),
     "sbmf_fm_query_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
@@ -169,6 +181,8 @@ SIGNATURES = {
     "sbmf_test_rccl_selftest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(RcclSelftest)]),
     "sbmf_test_device_usage": (C.c_int, [C.c_int, C.POINTER(DeviceUsage)]),
     "sbmf_test_watch_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
+    "sbmf_test_samples_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
+    "sbmf_test_samples_tune": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int]),
 }
 
 
