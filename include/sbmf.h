@@ -501,6 +501,79 @@ int sbmf_load_samples(sbmf_ctx* ctx, const char* path);
 int sbmf_samples_file_info(const char* path, uint32_t* version, uint32_t* precision, uint32_t* num_users,
                            uint32_t* num_items, uint32_t* num_factor, uint32_t* count, uint32_t* bias, uint64_t* bytes);
 
+/* --- sample store: fold-in guests after the run ------------------------------------------- */
+/* Not a reference interface.  A user who turns up after training, served from
+ * the stored samples with no sweep run: the guest's factor row at sample s is
+ * the user half's coordinate loop against V_s (the fold-in list's draw, above),
+ * which needs sigma_u, mu_u and tau of the sweep the sample came from.  The
+ * store keeps them on the host beside every sample it keeps, and they travel
+ * in a companion file of their own (the sample file does not change).
+ *
+ * sbmf_get_sample_hyper: sample s (as sbmf_get_sample) its [sigma_u | mu_u |
+ * sigma_v | mu_v], 4 K doubles in sbmf_get_hyper's layout, and tau: the values
+ * the halves of that sweep used.  Either pointer may be NULL.  Works with the
+ * biased quirk sets too.  SBMF_E_STATE for samples without hyperparameters:
+ * sbmf_load_samples replaces the samples and so clears them; loading the
+ * companion file (sbmf_load_samples_hyper) sets them. */
+int sbmf_get_sample_hyper(sbmf_ctx* ctx, uint32_t s, double* hyper4k, double* tau);
+/* The samples' hyperparameters to and from a little-endian companion file (the
+ * format: INTEGRATION.md 3e).  Loading needs a store whose count, K and
+ * per-sample sweep indices equal the file's -- the store the sample file saved
+ * beside it was loaded into -- else SBMF_E_ARG naming the field (or the first
+ * sample whose sweep index differs) and both values.  File errors are
+ * SBMF_E_IO. */
+int sbmf_save_samples_hyper(sbmf_ctx* ctx, const char* path);
+int sbmf_load_samples_hyper(sbmf_ctx* ctx, const char* path);
+/* Reads and validates a companion file's header alone (no context, no GPU), as
+ * sbmf_samples_file_info does for a sample file, with the same kinds of
+ * message; bytes = 24 + 4 count + 8 count (4 K + 1). */
+int sbmf_samples_hyper_file_info(const char* path, uint32_t* version, uint32_t* num_factor, uint32_t* count,
+                                 uint64_t* bytes);
+/* sbmf_foldin_recommend from the stored samples, stateless: each call names the
+ * n guests as the CSR of sbmf_foldin_users (ptr [n + 1], items, ratings; a
+ * guest may have no ratings, an item may repeat) and re-draws.  Per guest one
+ * row is carried from the oldest sample (entered with a zero row) to the
+ * newest: at each sample `scans` (1..64) coordinate scans against V_s with
+ * that sample's sigma_u, mu_u and tau, scan r taking the Philox normals
+ * 256 r + k of the key (seed, sample's absolute sweep index, tag 7, guest g)
+ * -- sbmf_philox_normals(seed, sweep, 7, g, 256 scans) lists them -- and every
+ * scan starting from e_j = r_j - u . v_j; after the last scan the row is
+ * rounded to the context's precision.  With scans = 1 and a store of every = 1
+ * kept from the sweep a fold-in list was registered at, the rows, scores and
+ * lists are that list's, bit for bit.  A thinned store's consecutive samples
+ * are far apart: more scans let the row forget the previous sample's.  The
+ * seed and quirks (s_is_var) are this context's: reproducing an in-chain
+ * list's numbers from a file needs the training run's seed and quirks.
+ * The scores of guest g at sample s are row_s[g] . V_s[j]; key, order, tie
+ * rule, outputs [n][topn] and empty slots as sbmf_recommend.  flags bit 0: keep
+ * the guest's own items; bit 1: clamp each sample's score.  All arithmetic in
+ * f64, every sum in a fixed order, no atomics: a rerun is bit-identical, and
+ * calls agree with each other.  Guests are processed in slices of whole groups
+ * of 64 whose two [rows][Jp] sums and rows stay within 1 GiB; every temporary
+ * is allocated for the call and freed after it (a failure is SBMF_E_NOMEM with
+ * the byte count).  stdev may be NULL; with one sample it is exactly 0.
+ * Scope: the SBPMF sampler, the unbiased quirk sets, both precisions, both RNG
+ * modes, one rank.  SBMF_E_STATE: what the store refuses; no sample kept yet; a
+ * store with biases (a guest bias would need a draw of its own); samples
+ * without hyperparameters (sbmf_load_samples_hyper).  SBMF_E_ARG: scans 0 or
+ * above 64, topn outside 1..1024, an item id >= num_items, a decreasing ptr,
+ * unknown flags. */
+int sbmf_samples_foldin_recommend(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items,
+                                  const double* ratings, uint32_t scans, uint32_t topn, uint32_t flags, double risk,
+                                  uint32_t* out_items, double* mean, double* stdev);
+/* The guests' rows themselves: rows [count][n][K] as doubles, oldest sample
+ * first. */
+int sbmf_samples_foldin_rows(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                             uint32_t scans, double* rows);
+/* One guest's (guest 0: its `len` items and ratings) full row, mean[j] and
+ * stdev[j] for j < num_items: exactly the values sbmf_samples_foldin_recommend
+ * ranks by.  flags bit 1: clamp. */
+int sbmf_samples_foldin_scores(sbmf_ctx* ctx, uint32_t len, const uint32_t* items, const double* ratings, uint32_t scans,
+                               uint32_t flags, double* mean, double* stdev);
+/* Device time (HIP events), ms, of the last of the three calls above (its last
+ * slice): the draw, the scoring launch and the selection; 0 before the first. */
+int sbmf_samples_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select);
+
 /* --- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------------------- */
 /* 128-byte RCCL unique id, produced by rank 0 and shared by the launcher. */
 int sbmf_comm_unique_id(uint8_t id[128]);
@@ -890,8 +963,10 @@ int sbmf_test_watch_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
 /* The same for the sample store's scoring launch (a sample's user rows, their biases and ids). */
 int sbmf_test_samples_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
 /* The sample store's scoring, for tests and measurements: budget_bytes replaces the 1 GiB of
- * sbmf_samples_recommend's temporaries (0: the default); unfused != 0 scores with one launch of the
- * watch list's kernel per stored sample into sums in memory in place of the fused kernel. */
+ * sbmf_samples_recommend's temporaries (0: the default); unfused bit 0 scores with one launch of the
+ * watch list's kernel per stored sample into sums in memory in place of the fused kernel; bit 1 draws
+ * the guests of sbmf_samples_foldin_* with the one fused launch (the sample loop inside) in place of
+ * the default, one launch per sample and scan (the faster form on the device: DESIGN.md 4.8). */
 int sbmf_test_samples_tune(sbmf_ctx* ctx, uint64_t budget_bytes, int unfused);
 
 #ifdef __cplusplus

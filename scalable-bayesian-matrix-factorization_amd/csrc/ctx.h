@@ -30,6 +30,7 @@
 #include "foldin.h"
 #include "recommend.h"
 #include "samples.h"
+#include "samples_foldin.h"
 #include "vbo.h"
 
 struct sbmf_ctx;
@@ -126,25 +127,34 @@ struct ScoreList {
 // each a copy of U [I][Kp] and V [J][Kp] in the context's precision and, with the biased sampler,
 // of bu [I] and bv [J]; b0 and the sweep index of every slot stay on the host.  The oldest sample
 // is in slot `head`; every `every`-th collected sweep since registration is kept (`seen` counts
-// them), the newest overwriting the oldest once the ring is full.  Nothing here exists while
-// no store is registered (cap == 0).
+// them), the newest overwriting the oldest once the ring is full.  Beside b0 the host keeps, by
+// slot, the hyperparameters the sweep's halves used -- [sig_u | mu_u | sig_v | mu_v] and tau, 4 K + 1
+// doubles -- which a guest's draw at that sample needs (sbmf_samples_foldin_*); has_hyper is
+// cleared by sbmf_load_samples, whose file does not hold them, and set by
+// sbmf_load_samples_hyper.  Nothing here exists while no store is registered (cap == 0).
 struct SampleStore {
     uint32_t cap = 0, every = 1, head = 0, count = 0, seen = 0;
     size_t bytes = 0;  // device bytes of the slots
     DBuf d_U, d_V, d_bu, d_bv;
     std::vector<double> b0;       // [cap], by slot
     std::vector<uint32_t> sweep;  // [cap], by slot
+    std::vector<double> hyper;    // [cap][4 K + 1], by slot: sbmf_get_hyper's block, then tau
+    bool has_hyper = false;       // every kept sample's entry of `hyper` is its sweep's
     hipEvent_t cev[2] = {}, scv[2] = {}, sel[2] = {};  // the last copy, scoring and selection [begin, end]
     bool timed_copy = false, timed_score = false, timed_select = false;
+    // the last guest call (sbmf_samples_foldin_*): its draw, scoring and selection [begin, end]
+    hipEvent_t gdr[2] = {}, gsc[2] = {}, gse[2] = {};
+    bool timed_gdraw = false, timed_gscore = false, timed_gselect = false;
     // test hook (sbmf_test_samples_tune): the temporaries' budget in bytes (0: the default) and
-    // the per-sample loop of launch_watch_accum in the fused kernel's place
+    // the per-sample loop of launch_watch_accum in the fused kernel's place; and the guests' draw
+    // by the one fused launch in place of the default, one launch per sample and scan
     uint64_t budget = 0;
-    bool unfused = false;
+    bool unfused = false, fused_draw = false;
     uint32_t slot(uint32_t s) const { return (head + s) % cap; }  // of the s-th oldest sample
     void alloc(sbmf_ctx* c, uint32_t cap_, uint32_t every_);
     void drop();
     template <typename T>
-    void keep(sbmf_ctx* c, double b0_, hipStream_t se);  // this sweep's tables into the next slot, if it is one to keep
+    void keep(sbmf_ctx* c, const Hyper& hy, hipStream_t se);  // this sweep's tables into the next slot, if it is one to keep
 };
 
 struct sbmf_ctx {

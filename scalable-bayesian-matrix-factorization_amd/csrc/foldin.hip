@@ -4,46 +4,12 @@
 // The guests' scores, rated-item mask and selection are the watch list's kernels (recommend.hip).
 #include "foldin.h"
 
-#include <cmath>
-
-#include "rng.h"
+#include "foldin_dev.h"
 
 namespace sbmf {
 
-typedef double fd4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ void fload4(const T* p, double (&b)[4]);
-template <>
-__device__ __forceinline__ void fload4<double>(const double* p, double (&b)[4]) {
-    const double2 x = *reinterpret_cast<const double2*>(p), y = *reinterpret_cast<const double2*>(p + 2);
-    b[0] = x.x, b[1] = x.y, b[2] = y.x, b[3] = y.y;
-}
-template <>
-__device__ __forceinline__ void fload4<float>(const float* p, double (&b)[4]) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    b[0] = (double)x.x, b[1] = (double)x.y, b[2] = (double)x.z, b[3] = (double)x.w;
-}
-
-// One workgroup of FOLDIN_NW = 16 waves per guest, the longest guests first (order[]): a guest
-// is one chain of dependent steps, so the launch takes as long as its longest row, and the
-// waves and the eight gathers a wave keeps in flight are what shorten that.
-// The row u, its normals and the sweep's [sg | mu] sit in LDS; the residuals e_j in the
-// guest's slice of the device scratch E (a row may be longer than any LDS: the kernel loops
-// over it and holds none of it in registers).
-// Per block of 16 columns k0..k0+15, with S the [n_g][16] slice of the rated items' V rows:
-//   1. a wave takes every 16th vector of 4 ratings, eight of them per trip: lane l holds
-//      S[4 vec + (l >> 4)][l & 15] -- 16 lanes read 128 contiguous bytes of a V row (f32: 64) -- and one MFMA f64 16x16x4
-//      with A = B = that value adds the vector's part of S^T S: A[m][k] from lane m + 16 k,
-//      B[k][n] from lane n + 16 k, D[(l >> 4) + 4 i][l & 15] in acc[i]
-//      (tests/hip/mfma_layout.hip); c = S^T e by one FMA per lane
-//   2. the waves' partial G and c are added in wave (then quarter-wave) order in LDS
-//   3. wave 0 makes the 16 draws in order: lane m holds c_m, which after draw j < m loses
-//      G[m][j] d_j -- the coordinate loop's residual update, seen through S^T
-//   4. e_j -= S[j] . d, one thread per rating (its 128 bytes of the row again)
-// Step 4 is skipped after the last block: nothing reads the residuals then.
-constexpr uint32_t FOLDIN_NW = 16, FOLDIN_NT = 64 * FOLDIN_NW, FOLDIN_UNROLL = 8;
-
+// One workgroup per guest (foldin_dev.h): the row, the sweep's [sg | mu] and the normals into LDS,
+// one scan against the sweep's V, the row rounded once on store.
 template <typename T>
 __global__ __launch_bounds__(FOLDIN_NT) void k_foldin(const uint32_t* __restrict__ order, const uint32_t* __restrict__ ptr,
                                                       const uint32_t* __restrict__ items,
@@ -51,123 +17,19 @@ __global__ __launch_bounds__(FOLDIN_NT) void k_foldin(const uint32_t* __restrict
                                                       const T* __restrict__ V, uint32_t K, uint32_t Kp,
                                                       const double* __restrict__ hyper, double tau, int sd_is_var,
                                                       uint64_t seed, uint32_t sweep, double* E) {
-    __shared__ double urow[FOLDIN_KP_MAX], zs[FOLDIN_KP_MAX], hyp[2 * FOLDIN_KP_MAX];
-    __shared__ double Gw[FOLDIN_NW][256], Gs[16 * 17], cw[FOLDIN_NW][4][16], cs[16], D[16];
+    __shared__ FoldinLds L;
     const uint32_t g = order[blockIdx.x], tid = threadIdx.x;
-    const uint32_t lane = tid & 63, wave = tid >> 6, col = lane & 15, q = lane >> 4;
     const uint32_t beg = ptr[g], ng = ptr[g + 1] - beg;
-    const uint32_t* it = items + beg;
-    double* e = E + beg;
     T* grow = G + (size_t)g * Kp;
     for (uint32_t k = tid; k < Kp; k += FOLDIN_NT) {
-        urow[k] = (double)grow[k];
-        hyp[k] = hyper[k];
-        hyp[FOLDIN_KP_MAX + k] = hyper[Kp + k];
+        L.urow[k] = (double)grow[k];
+        L.hyp[k] = hyper[k];
+        L.hyp[FOLDIN_KP_MAX + k] = hyper[Kp + k];
     }
-    for (uint32_t p = tid; p < Kp / 2; p += FOLDIN_NT) philox_normal_pair(seed, g, sweep, TAG_GUEST, p, zs[2 * p], zs[2 * p + 1]);
+    foldin_normals(L, seed, g, sweep, 0, Kp, tid);
     __syncthreads();
-    // e_j = r_j - u . v_j
-    for (uint32_t j = tid; j < ng; j += FOLDIN_NT) {
-        const T* vp = V + (size_t)it[j] * Kp;
-        double s = 0.0;
-        for (uint32_t k = 0; k < Kp; k += 4) {
-            double b[4];
-            fload4<T>(vp + k, b);
-#pragma unroll
-            for (int x = 0; x < 4; ++x) s = fma(urow[k + x], b[x], s);
-        }
-        e[j] = ratings[beg + j] - s;
-    }
-    __syncthreads();
-    for (uint32_t k0 = 0; k0 < Kp; k0 += 16) {
-        // 1. this wave's part of G_B and c
-        fd4 acc = fd4{0, 0, 0, 0};
-        double cp = 0.0;
-        for (uint32_t v0 = 4 * wave; v0 < ng; v0 += 4 * FOLDIN_NW * FOLDIN_UNROLL) {
-            uint32_t row[FOLDIN_UNROLL];
-            double v[FOLDIN_UNROLL], ej[FOLDIN_UNROLL];
-#pragma unroll
-            for (uint32_t x = 0; x < FOLDIN_UNROLL; ++x) {
-                const uint32_t j = v0 + x * 4 * FOLDIN_NW + q;
-                row[x] = j < ng ? it[j] : 0u;
-            }
-#pragma unroll
-            for (uint32_t x = 0; x < FOLDIN_UNROLL; ++x) {
-                const uint32_t j = v0 + x * 4 * FOLDIN_NW + q;
-                v[x] = ej[x] = 0.0;
-                if (j < ng) {  // a slot past the row adds zeros
-                    v[x] = (double)V[(size_t)row[x] * Kp + k0 + col];
-                    ej[x] = e[j];
-                }
-            }
-#pragma unroll
-            for (uint32_t x = 0; x < FOLDIN_UNROLL; ++x) {
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[x], v[x], acc, 0, 0, 0);
-                cp = fma(v[x], ej[x], cp);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Gw[wave][(q + 4 * i) * 16 + col] = acc[i];
-        cw[wave][q][col] = cp;
-        __syncthreads();
-        // 2. the waves' sums, in wave order
-        if (tid < 256) {
-            double s = 0.0;
-#pragma unroll
-            for (uint32_t w = 0; w < FOLDIN_NW; ++w) s += Gw[w][tid];
-            Gs[(tid >> 4) * 17 + (tid & 15)] = s;
-        }
-        if (tid < 16) {
-            double s = 0.0;
-#pragma unroll
-            for (uint32_t w = 0; w < FOLDIN_NW; ++w)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) s += cw[w][x][tid];
-            cs[tid] = s;
-        }
-        __syncthreads();
-        // 3. the block's 16 draws (every quarter of wave 0 computes them; the first one stores)
-        if (wave == 0) {
-            const uint32_t k = k0 + col;
-            const bool kin = k < K;
-            const double P = Gs[col * 17 + col], uo = urow[k];
-            const double sg = hyp[k], mu = hyp[FOLDIN_KP_MAX + k], z = zs[k];
-            const double var = kin ? 1.0 / (sg + tau * P) : 0.0;
-            const double sd = sd_is_var ? var : sqrt(var);
-            double cm = cs[col], un = 0.0;
-            for (uint32_t j = 0; j < 16; ++j) {
-                // lane j's c is final here: c_j = sum v_jk e_j with the earlier draws applied
-                const double Q = cm + P * uo;
-                const double mean = var * (tau * Q + sg * mu);
-                const double cand = kin ? mean + sd * z : 0.0;
-                const double dj = __shfl(cand - uo, (int)j, 16);
-                if (col == j) un = cand;
-                if (col > j) cm -= Gs[col * 17 + j] * dj;
-            }
-            if (q == 0) {
-                urow[k] = un;
-                D[col] = un - uo;
-            }
-        }
-        __syncthreads();
-        // 4. the residuals
-        if (k0 + 16 < Kp) {
-            for (uint32_t j = tid; j < ng; j += FOLDIN_NT) {
-                const T* vp = V + (size_t)it[j] * Kp + k0;
-                double s = 0.0;
-#pragma unroll
-                for (int x4 = 0; x4 < 16; x4 += 4) {
-                    double b[4];
-                    fload4<T>(vp + x4, b);
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) s = fma(b[x], D[x4 + x], s);
-                }
-                e[j] -= s;
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t k = tid; k < Kp; k += FOLDIN_NT) grow[k] = (T)urow[k];  // padding columns: zero
+    foldin_scan<T>(L, items + beg, ratings + beg, E + beg, ng, V, K, Kp, tau, sd_is_var, tid);
+    for (uint32_t k = tid; k < Kp; k += FOLDIN_NT) grow[k] = (T)L.urow[k];  // padding columns: zero
 }
 
 template <typename T>

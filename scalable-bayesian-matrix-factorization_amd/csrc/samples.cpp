@@ -1,7 +1,9 @@
 // samples.cpp -- the posterior sample store (SampleStore, ctx.h) and its entry points: keeping
 // thinned samples of the SBPMF chain on the device (sbmf_keep_samples; the copy runs in the sweep's
 // evaluation, sweep.cpp), scoring users and pairs from them after the run (samples.hip), and the
-// sample file (sbmf_save_samples / sbmf_load_samples / sbmf_samples_file_info).
+// sample file (sbmf_save_samples / sbmf_load_samples / sbmf_samples_file_info); the
+// samples' hyperparameters, their companion file, and guests drawn from the stored samples after the
+// run (sbmf_samples_foldin_*; samples_foldin.hip).
 #include <sys/stat.h>
 
 #include "ctx.h"
@@ -212,6 +214,199 @@ void load_T(sbmf_ctx* c, FILE* f, const char* path, uint32_t count) {
 // the temporaries' budget of sbmf_samples_recommend: S1 and S2 of one slice of users
 constexpr uint64_t kBudget = 1ull << 30;
 
+// ------------------------------------------------------------------ the hyperparameters' file
+constexpr char kHyperMagic[8] = {'S', 'B', 'M', 'F', 'S', 'H', 'P', '\n'};
+constexpr uint32_t kHyperVersion = 1;
+struct HyperHeader {  // 24 bytes
+    char magic[8];
+    uint32_t version, K, count, reserved;
+};
+static_assert(sizeof(HyperHeader) == 24, "the companion file's header is 24 bytes");
+uint64_t hyper_file_bytes(const HyperHeader& h) {
+    return sizeof(HyperHeader) + (uint64_t)h.count * 4 + (uint64_t)h.count * (4 * (uint64_t)h.K + 1) * 8;
+}
+// open_sample_file for the companion file
+void open_hyper_file(const char* fn, const char* path, File& file, HyperHeader& h) {
+    file.f = std::fopen(path, "rb");
+    struct stat sb;
+    if (!file.f || fstat(fileno(file.f), &sb) != 0) sbmf::fail(SBMF_E_IO, "%s: cannot open %s", fn, path);
+    const uint64_t size = (uint64_t)sb.st_size;
+    if (size < sizeof(HyperHeader) || std::fread(&h, sizeof(HyperHeader), 1, file.f) != 1)
+        sbmf::fail(SBMF_E_IO, "%s: %s is truncated in its header: %llu bytes, a sample hyperparameter file's header has %zu",
+                   fn, path, (unsigned long long)size, sizeof(HyperHeader));
+    if (std::memcmp(h.magic, kHyperMagic, sizeof kHyperMagic) != 0)
+        sbmf::fail(SBMF_E_IO, "%s: %s is not a sample hyperparameter file (bad magic)", fn, path);
+    if (h.version != kHyperVersion)
+        sbmf::fail(SBMF_E_IO, "%s: %s has the unknown format version %u; this build reads version %u", fn, path, h.version,
+                   kHyperVersion);
+    if (h.K == 0 || h.K > 256 || h.count > 65535 || h.reserved != 0)
+        sbmf::fail(SBMF_E_IO, "%s: %s has a bad header (K %u, count %u, reserved %u)", fn, path, h.K, h.count, h.reserved);
+    const uint64_t want = hyper_file_bytes(h);
+    if (size < want)
+        sbmf::fail(SBMF_E_IO, "%s: %s is truncated in its body: %llu bytes, its header implies %llu", fn, path,
+                   (unsigned long long)size, (unsigned long long)want);
+    if (size > want)
+        sbmf::fail(SBMF_E_IO, "%s: %s has %llu trailing bytes: %llu bytes, its header implies %llu", fn, path,
+                   (unsigned long long)(size - want), (unsigned long long)size, (unsigned long long)want);
+}
+
+// ------------------------------------------------------------------ guests from the stored samples
+// What the three guest calls check before anything is allocated.
+void guests_ready(sbmf_ctx* c, const char* fn, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                  uint32_t scans) {
+    samples_scope(c, fn);
+    if (c->bias)
+        sbmf::fail(SBMF_E_STATE, "%s: guests are folded into a store of the unbiased quirk sets (final, sbpmf2, none); a "
+                                 "guest bias would need a draw of its own", fn);
+    if (scans < 1 || scans > sbmf::SAMPLES_FOLDIN_SCANS_MAX)
+        sbmf::fail(SBMF_E_ARG, "%s: scans %u is not in 1..%u", fn, scans, sbmf::SAMPLES_FOLDIN_SCANS_MAX);
+    if (n && !ptr) sbmf::fail(SBMF_E_ARG, "%s: null ptr with n > 0", fn);
+    if (n >= 0xfffffffeu) sbmf::fail(SBMF_E_ARG, "%s: %u guests are too many", fn, n);
+    for (uint32_t g = 0; g < n; ++g)
+        if (ptr[g + 1] < ptr[g]) sbmf::fail(SBMF_E_ARG, "%s: ptr decreases at guest %u (%u then %u)", fn, g, ptr[g], ptr[g + 1]);
+    const uint32_t p0 = n ? ptr[0] : 0, nnz = n ? ptr[n] - p0 : 0;
+    if (nnz && (!items || !ratings)) sbmf::fail(SBMF_E_ARG, "%s: null items / ratings with ratings listed", fn);
+    for (uint32_t q = 0; q < nnz; ++q)
+        if (items[p0 + q] >= c->J)
+            sbmf::fail(SBMF_E_ARG, "%s: items[%u] = %u is not below the %u items", fn, p0 + q, items[p0 + q], c->J);
+    samples_ready(c, fn);
+    if (!c->samples.has_hyper)
+        sbmf::fail(SBMF_E_STATE, "%s: the stored samples have no hyperparameters (a sample file holds none: "
+                                 "sbmf_load_samples_hyper loads its companion file)", fn);
+}
+
+// One guest call: the guests' CSR and what the draw reads of the samples on the device, the
+// slices' temporaries, and the draw / scoring of one slice.  Everything is freed with the object.
+struct GuestCall {
+    sbmf_ctx* c;
+    const char* fn;
+    uint32_t n, nnz, scans, rows = 0;  // rows: guests per slice
+    size_t gs = 0;                     // elements of one sample's GS table: (rows + 2) Kp
+    sbmf::DBuf d_ptr, d_items, d_ratings, d_order, d_ident, d_E, d_hyp, d_tau, d_sw, d_GS, d_S1, d_S2, d_b0;
+    std::vector<uint32_t> hp;  // the CSR's ptr, from 0
+    sbmf::SamplesFoldinArgs a;
+
+    // sums: the slice also holds S1 / S2 [rows][Jp] (else only the rows are wanted)
+    GuestCall(sbmf_ctx* c_, const char* fn_, uint32_t n_, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+              uint32_t scans_, bool sums)
+        : c(c_), fn(fn_), n(n_), nnz(n_ ? ptr[n_] - ptr[0] : 0), scans(scans_) {
+        const SampleStore& ss = c->samples;
+        const uint32_t K = c->K, Kp = c->Kp, Jp = sbmf::watch_jp(c->J), count = ss.count;
+        const size_t ts = sbmf::tsize(c);
+        // guests per slice: as many as the budget holds of two sums' rows and `count` factor rows,
+        // in whole workgroups of 64, one at least
+        const uint64_t budget = ss.budget ? ss.budget : kBudget;
+        const uint64_t per = (sums ? (uint64_t)2 * Jp * sizeof(double) : 0) + (uint64_t)count * Kp * ts;
+        rows = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(budget / per / 64 * 64, 64));
+        gs = ((size_t)rows + 2) * Kp;
+        const size_t b_GS = (size_t)count * gs * ts, b_sum = sums ? (size_t)rows * Jp * sizeof(double) : 0;
+        const size_t b_tot = b_GS + 2 * b_sum + ((size_t)n + 1 + 3 * (size_t)n + nnz + count) * sizeof(uint32_t) +
+                             ((size_t)2 * nnz + (size_t)count * (2 * Kp + 1)) * sizeof(double) +
+                             (ss.fused_draw ? 0 : (size_t)rows * Kp * sizeof(double));
+        try {
+            hipStream_t st = c->st;
+            const uint32_t p0 = ptr[0];
+            hp.resize(n + 1);
+            for (uint32_t g = 0; g <= n; ++g) hp[g] = ptr[g] - p0;  // the device CSR starts at 0
+            std::vector<uint32_t> ident(n), sw(count);
+            std::iota(ident.begin(), ident.end(), 0u);
+            // within each slice the launch ends with its longest row: those start first
+            std::vector<uint32_t> order(ident);
+            for (uint32_t off = 0; off < n; off += rows)
+                std::stable_sort(order.begin() + off, order.begin() + std::min(n, off + rows),
+                                 [&](uint32_t x, uint32_t y) { return hp[x + 1] - hp[x] > hp[y + 1] - hp[y]; });
+            // the samples' [sig_u | mu_u], tau and sweep index, oldest first
+            std::vector<double> hyp((size_t)count * 2 * Kp, 0.0), tau(count);
+            for (uint32_t s = 0; s < count; ++s) {
+                const uint32_t p = ss.slot(s);
+                const double* h = ss.hyper.data() + (size_t)p * (4 * K + 1);
+                std::copy(h, h + K, hyp.begin() + (size_t)s * 2 * Kp);
+                std::copy(h + K, h + 2 * K, hyp.begin() + (size_t)s * 2 * Kp + Kp);
+                tau[s] = h[4 * K];
+                sw[s] = ss.sweep[p];
+            }
+            // (the per-launch form's carry [rows][Kp] doubles sits behind GS in the same allocation)
+            d_GS.alloc(b_GS + (ss.fused_draw ? 0 : (size_t)rows * Kp * sizeof(double)));
+            if (sums) {
+                d_S1.alloc(b_sum);
+                d_S2.alloc(b_sum);
+            }
+            d_E.alloc((size_t)nnz * sizeof(double));
+            d_items.alloc((size_t)nnz * sizeof(uint32_t));
+            d_ratings.alloc((size_t)nnz * sizeof(double));
+            sbmf::upload(d_ptr, hp, st);
+            sbmf::upload(d_order, order, st);
+            sbmf::upload(d_ident, ident, st);
+            sbmf::upload(d_hyp, hyp, st);
+            sbmf::upload(d_tau, tau, st);
+            sbmf::upload(d_sw, sw, st);
+            if (nnz) {
+                HIPCHK(hipMemcpyAsync(d_items.p, items + p0, (size_t)nnz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_ratings.p, ratings + p0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
+            }
+            a.sv = view_of(c, d_b0, st);
+            HIPCHK(hipStreamSynchronize(st));  // the vectors are locals
+        } catch (const sbmf::Error& e) {
+            if (e.code == SBMF_E_NOMEM)
+                sbmf::fail(SBMF_E_NOMEM, "%s: %u guests with %u ratings at %u samples need %zu bytes of device memory: %s", fn,
+                           n, nnz, count, b_tot, e.msg.c_str());
+            throw;
+        }
+        // A sample's GS table sits at its ring slot, so the scoring kernel reads GS through the
+        // store's own view (one head and cap for both sides): a store that has not wrapped has
+        // head 0, a wrapped one is full -- the `count` slots in use are 0..count-1 either way.
+        a.GS = d_GS.p;
+        a.gs = gs;
+        a.ptr = d_ptr.as<uint32_t>();
+        a.items = d_items.as<uint32_t>();
+        a.ratings = d_ratings.as<double>();
+        a.K = K;
+        a.Kp = Kp;
+        a.hyper = d_hyp.as<double>();
+        a.tau = d_tau.as<double>();
+        a.sweeps = d_sw.as<uint32_t>();
+        a.scans = scans;
+        a.sd_is_var = c->sd_is_var;
+        a.seed = c->cfg.seed;
+        a.E = d_E.as<double>();
+    }
+
+    // the rows of the guests off .. off + m - 1 at every sample into GS (events: ss.gdr)
+    template <typename T>
+    void draw_T(uint32_t off, uint32_t m) {
+        SampleStore& ss = c->samples;
+        hipStream_t st = c->st;
+        a.n = m;
+        a.g0 = off;
+        a.order = d_order.as<uint32_t>() + off;
+        HIPCHK(hipMemsetAsync(d_GS.p, 0, d_GS.bytes, st));
+        HIPCHK(hipEventRecord(ss.gdr[0], st));
+        if (ss.fused_draw) {
+            HIPCHK(sbmf::launch_samples_foldin<T>(a, st));
+        } else {  // the memset above zeroed the carry too
+            double* carry = reinterpret_cast<double*>(static_cast<char*>(d_GS.p) + (size_t)ss.count * gs * sizeof(T));
+            for (uint32_t s = 0; s < ss.count; ++s)
+                for (uint32_t r = 0; r < scans; ++r) HIPCHK(sbmf::launch_samples_foldin_step<T>(a, s, r, carry, st));
+        }
+        HIPCHK(hipEventRecord(ss.gdr[1], st));
+        ss.timed_gdraw = true;
+    }
+    void draw(uint32_t off, uint32_t m) {
+        c->cfg.precision == SBMF_F32 ? draw_T<float>(off, m) : draw_T<double>(off, m);
+    }
+    // S1 / S2 of the slice just drawn: the store's scoring kernel, GS in U's place, rows 0..m-1
+    void score(uint32_t m, int clamp) {
+        SampleStore& ss = c->samples;
+        sbmf::SampleView v = a.sv;
+        v.U = d_GS.p;
+        v.su = gs;
+        HIPCHK(hipEventRecord(ss.gsc[0], c->st));
+        score_rows(c, v, d_ident.as<uint32_t>(), m, clamp, d_S1.as<double>(), d_S2.as<double>(), c->st);
+        HIPCHK(hipEventRecord(ss.gsc[1], c->st));
+        ss.timed_gscore = true;
+    }
+};
+
 }  // namespace
 
 void SampleStore::alloc(sbmf_ctx* c, uint32_t cap_, uint32_t every_) {
@@ -222,32 +417,37 @@ void SampleStore::alloc(sbmf_ctx* c, uint32_t cap_, uint32_t every_) {
         d_bu.alloc((size_t)cap_ * I * sizeof(double));
         d_bv.alloc((size_t)cap_ * J * sizeof(double));
     }
-    for (hipEvent_t* e : {cev, scv, sel}) {
+    for (hipEvent_t* e : {cev, scv, sel, gdr, gsc, gse}) {
         sbmf::event_create(&e[0]);
         sbmf::event_create(&e[1]);
     }
     b0.assign(cap_, 0.0);
     sweep.assign(cap_, 0);
+    hyper.assign((size_t)cap_ * (4 * c->K + 1), 0.0);
+    has_hyper = true;  // of every sample kept from here on; a loaded file's have none
     cap = cap_;
     every = every_;
     bytes = (size_t)cap_ * slot_bytes(c);
 }
 void SampleStore::drop() {
     for (sbmf::DBuf* d : {&d_U, &d_V, &d_bu, &d_bv}) d->release();
-    for (hipEvent_t* e : {cev, scv, sel}) {
+    for (hipEvent_t* e : {cev, scv, sel, gdr, gsc, gse}) {
         sbmf::event_destroy(e[0]);
         sbmf::event_destroy(e[1]);
     }
     b0.clear();
     sweep.clear();
+    hyper.clear();
+    has_hyper = false;
     cap = head = count = seen = 0;
     every = 1;
     bytes = 0;
     timed_copy = timed_score = timed_select = false;
+    timed_gdraw = timed_gscore = timed_gselect = false;
 }
 // (the caller has checked that the sweep is a collected one)
 template <typename T>
-void SampleStore::keep(sbmf_ctx* c, double b0_, hipStream_t se) {
+void SampleStore::keep(sbmf_ctx* c, const Hyper& hy, hipStream_t se) {
     if (seen++ % every) return;
     const uint32_t p = count < cap ? slot(count) : head;  // the next free slot, or the oldest sample's
     const size_t I = c->I, J = c->J, Kp = c->Kp;
@@ -260,14 +460,21 @@ void SampleStore::keep(sbmf_ctx* c, double b0_, hipStream_t se) {
     }
     HIPCHK(hipEventRecord(cev[1], se));
     timed_copy = true;
-    b0[p] = b0_;
+    b0[p] = hy.b0;
     sweep[p] = c->sweep;
+    const size_t K = c->K;
+    double* h = hyper.data() + (size_t)p * (4 * K + 1);
+    std::copy(hy.sig_u.begin(), hy.sig_u.begin() + K, h);
+    std::copy(hy.mu_u.begin(), hy.mu_u.begin() + K, h + K);
+    std::copy(hy.sig_v.begin(), hy.sig_v.begin() + K, h + 2 * K);
+    std::copy(hy.mu_v.begin(), hy.mu_v.begin() + K, h + 3 * K);
+    h[4 * K] = hy.tau;
     if (count < cap) count++;
     else head = (head + 1) % cap;
     c->launches += c->bias ? 4 : 2;
 }
-template void SampleStore::keep<float>(sbmf_ctx*, double, hipStream_t);
-template void SampleStore::keep<double>(sbmf_ctx*, double, hipStream_t);
+template void SampleStore::keep<float>(sbmf_ctx*, const Hyper&, hipStream_t);
+template void SampleStore::keep<double>(sbmf_ctx*, const Hyper&, hipStream_t);
 
 extern "C" {
 
@@ -542,6 +749,7 @@ int sbmf_load_samples(sbmf_ctx* ctx, const char* path) {
         }
     }
     ss.head = ss.count = ss.seen = 0;
+    ss.has_hyper = false;  // the file holds none (sbmf_load_samples_hyper)
     std::vector<uint32_t> sweeps(h.count);
     if (std::fread(sweeps.data(), 4, h.count, file.f) != h.count) sbmf::fail(SBMF_E_IO, "%s: reading %s failed", fn, path);
     std::copy(sweeps.begin(), sweeps.end(), ss.sweep.begin());
@@ -569,11 +777,230 @@ int sbmf_samples_file_info(const char* path, uint32_t* version, uint32_t* precis
     API_END(ctx)
 }
 
+// --- the samples' hyperparameters and their file ------------------------------------------------
+int sbmf_get_sample_hyper(sbmf_ctx* ctx, uint32_t s, double* hyper4k, double* tau) {
+    API_BEGIN
+    const char* fn = "sbmf_get_sample_hyper";
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    samples_ready(ctx, fn);
+    const SampleStore& ss = ctx->samples;
+    if (s >= ss.count) sbmf::fail(SBMF_E_ARG, "%s: sample %u of %u kept", fn, s, ss.count);
+    if (!ss.has_hyper)
+        sbmf::fail(SBMF_E_STATE, "%s: the stored samples have no hyperparameters (a sample file holds none: "
+                                 "sbmf_load_samples_hyper loads its companion file)", fn);
+    const size_t K = ctx->K;
+    const double* h = ss.hyper.data() + (size_t)ss.slot(s) * (4 * K + 1);
+    if (hyper4k) std::copy(h, h + 4 * K, hyper4k);
+    if (tau) *tau = h[4 * K];
+    API_END(ctx)
+}
+
+int sbmf_save_samples_hyper(sbmf_ctx* ctx, const char* path) {
+    API_BEGIN
+    const char* fn = "sbmf_save_samples_hyper";
+    if (!ctx || !path) sbmf::fail(SBMF_E_ARG, "null argument");
+    samples_ready(ctx, fn);
+    const SampleStore& ss = ctx->samples;
+    if (!ss.has_hyper) sbmf::fail(SBMF_E_STATE, "%s: the stored samples have no hyperparameters to save", fn);
+    HyperHeader h{};
+    std::memcpy(h.magic, kHyperMagic, sizeof kHyperMagic);
+    h.version = kHyperVersion;
+    h.K = ctx->K;
+    h.count = ss.count;
+    File file;
+    file.f = std::fopen(path, "wb");
+    if (!file.f) sbmf::fail(SBMF_E_IO, "%s: cannot open %s for writing", fn, path);
+    const size_t per = 4 * (size_t)ctx->K + 1;
+    std::vector<uint32_t> sweeps(ss.count);
+    std::vector<double> body(ss.count * per);
+    for (uint32_t s = 0; s < ss.count; ++s) {
+        const uint32_t p = ss.slot(s);
+        sweeps[s] = ss.sweep[p];
+        std::copy(ss.hyper.begin() + p * per, ss.hyper.begin() + (p + 1) * per, body.begin() + s * per);
+    }
+    bool ok = std::fwrite(&h, sizeof h, 1, file.f) == 1 && std::fwrite(sweeps.data(), 4, sweeps.size(), file.f) == sweeps.size() &&
+              std::fwrite(body.data(), 8, body.size(), file.f) == body.size();
+    const int rc = std::fclose(file.f);
+    file.f = nullptr;
+    if (!ok || rc != 0) sbmf::fail(SBMF_E_IO, "%s: writing %s failed", fn, path);
+    API_END(ctx)
+}
+
+int sbmf_load_samples_hyper(sbmf_ctx* ctx, const char* path) {
+    API_BEGIN
+    const char* fn = "sbmf_load_samples_hyper";
+    if (!ctx || !path) sbmf::fail(SBMF_E_ARG, "null argument");
+    samples_scope(ctx, fn);
+    File file;
+    HyperHeader h;
+    open_hyper_file(fn, path, file, h);
+    samples_ready(ctx, fn);
+    SampleStore& ss = ctx->samples;
+    if (h.K != ctx->K) sbmf::fail(SBMF_E_ARG, "%s: %s holds num_factor K = %u; this context has K = %u", fn, path, h.K, ctx->K);
+    if (h.count != ss.count) sbmf::fail(SBMF_E_ARG, "%s: %s holds count = %u samples; the store holds %u", fn, path, h.count, ss.count);
+    const size_t per = 4 * (size_t)ctx->K + 1;
+    std::vector<uint32_t> sweeps(h.count);
+    std::vector<double> body(h.count * per);
+    if (std::fread(sweeps.data(), 4, sweeps.size(), file.f) != sweeps.size() ||
+        std::fread(body.data(), 8, body.size(), file.f) != body.size())
+        sbmf::fail(SBMF_E_IO, "%s: reading %s failed", fn, path);
+    for (uint32_t s = 0; s < h.count; ++s)
+        if (sweeps[s] != ss.sweep[ss.slot(s)])
+            sbmf::fail(SBMF_E_ARG, "%s: %s holds sweep index %u for sample %u; the store's sample %u is sweep %u", fn, path,
+                       sweeps[s], s, s, ss.sweep[ss.slot(s)]);
+    for (uint32_t s = 0; s < h.count; ++s)
+        std::copy(body.begin() + s * per, body.begin() + (s + 1) * per, ss.hyper.begin() + ss.slot(s) * per);
+    ss.has_hyper = true;
+    API_END(ctx)
+}
+
+int sbmf_samples_hyper_file_info(const char* path, uint32_t* version, uint32_t* num_factor, uint32_t* count, uint64_t* bytes) {
+    sbmf_ctx* ctx = nullptr;
+    API_BEGIN
+    if (!path) sbmf::fail(SBMF_E_ARG, "null path");
+    File file;
+    HyperHeader h;
+    open_hyper_file("sbmf_samples_hyper_file_info", path, file, h);
+    if (version) *version = h.version;
+    if (num_factor) *num_factor = h.K;
+    if (count) *count = h.count;
+    if (bytes) *bytes = hyper_file_bytes(h);
+    API_END(ctx)
+}
+
+// --- guests from the stored samples -----------------------------------------------------------
+int sbmf_samples_foldin_recommend(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items,
+                                  const double* ratings, uint32_t scans, uint32_t topn, uint32_t flags, double risk,
+                                  uint32_t* out_items, double* mean, double* stdev) {
+    API_BEGIN
+    const char* fn = "sbmf_samples_foldin_recommend";
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    samples_scope(ctx, fn);
+    if (n && (!out_items || !mean)) sbmf::fail(SBMF_E_ARG, "%s: null argument", fn);
+    if (topn < 1 || topn > 1024) sbmf::fail(SBMF_E_ARG, "%s: topn %u is not in 1..1024", fn, topn);
+    if (flags & ~3u)
+        sbmf::fail(SBMF_E_ARG, "%s: unknown flags 0x%x (bit 0 = keep the guest's own items, bit 1 = clamp)", fn, flags & ~3u);
+    if (!(risk == risk)) sbmf::fail(SBMF_E_ARG, "%s: risk is NaN", fn);
+    guests_ready(ctx, fn, n, ptr, items, ratings, scans);
+    if (n == 0) return SBMF_OK;
+    SampleStore& ss = ctx->samples;
+    hipStream_t st = ctx->st;
+    const uint32_t J = ctx->J, Jw = sbmf::watch_jw(J);
+    const bool exclude = !(flags & 1u);
+    GuestCall gc(ctx, fn, n, ptr, items, ratings, scans, true);
+    const uint32_t rows = gc.rows;
+    const size_t slots = (size_t)rows * topn;
+    sbmf::DBuf d_it, d_ms, d_mask;
+    try {
+        d_it.alloc(slots * sizeof(uint32_t));
+        d_ms.alloc(2 * slots * sizeof(double));
+        if (exclude) d_mask.alloc((size_t)rows * Jw * sizeof(uint32_t));
+    } catch (const sbmf::Error& e) {
+        if (e.code == SBMF_E_NOMEM)
+            sbmf::fail(SBMF_E_NOMEM, "%s: the selection of %u guests needs %zu bytes of device memory: %s", fn, rows,
+                       slots * (sizeof(uint32_t) + 2 * sizeof(double)) + (exclude ? (size_t)rows * Jw * sizeof(uint32_t) : 0),
+                       e.msg.c_str());
+        throw;
+    }
+    for (uint32_t off = 0; off < n; off += rows) {
+        const uint32_t m = std::min(rows, n - off);
+        const size_t ms = (size_t)m * topn, o = (size_t)off * topn;
+        gc.draw(off, m);
+        gc.score(m, (flags & 2u) ? 1 : 0);
+        HIPCHK(hipEventRecord(ss.gse[0], st));
+        if (exclude) {  // "rated": the guest's own items (the guest CSR in the user-side CSR's place)
+            HIPCHK(hipMemsetAsync(d_mask.p, 0, (size_t)m * Jw * sizeof(uint32_t), st));
+            HIPCHK(sbmf::launch_watch_mask(gc.d_ident.as<uint32_t>() + off, m, gc.d_ptr.as<uint32_t>(), gc.d_items.as<uint32_t>(),
+                                           d_mask.as<uint32_t>(), Jw, st));
+        }
+        HIPCHK(sbmf::launch_watch_select(m, gc.d_S1.as<double>(), gc.d_S2.as<double>(), J, (double)ss.count, risk,
+                                         exclude ? d_mask.as<uint32_t>() : nullptr, topn, d_it.as<uint32_t>(),
+                                         d_ms.as<double>(), d_ms.as<double>() + ms, st));
+        HIPCHK(hipEventRecord(ss.gse[1], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(out_items + o, d_it.p, ms * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mean + o, d_ms.p, ms * sizeof(double), hipMemcpyDeviceToHost));
+        if (stdev) HIPCHK(hipMemcpy(stdev + o, d_ms.as<double>() + ms, ms * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    ss.timed_gselect = true;
+    API_END(ctx)
+}
+
+int sbmf_samples_foldin_rows(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                             uint32_t scans, double* rows) {
+    API_BEGIN
+    const char* fn = "sbmf_samples_foldin_rows";
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    samples_scope(ctx, fn);
+    if (n && !rows) sbmf::fail(SBMF_E_ARG, "%s: null argument", fn);
+    guests_ready(ctx, fn, n, ptr, items, ratings, scans);
+    if (n == 0) return SBMF_OK;
+    const SampleStore& ss = ctx->samples;
+    const size_t K = ctx->K, Kp = ctx->Kp;
+    GuestCall gc(ctx, fn, n, ptr, items, ratings, scans, false);
+    auto fetch = [&](auto type, uint32_t off, uint32_t m) {
+        using T = decltype(type);
+        std::vector<T> h((size_t)m * Kp);
+        for (uint32_t s = 0; s < ss.count; ++s) {
+            HIPCHK(hipMemcpy(h.data(), gc.d_GS.as<T>() + (size_t)ss.slot(s) * gc.gs, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+            double* out = rows + ((size_t)s * n + off) * K;
+            for (size_t g = 0; g < m; ++g)
+                for (size_t k = 0; k < K; ++k) out[g * K + k] = (double)h[g * Kp + k];  // an f32 value widens exactly
+        }
+    };
+    for (uint32_t off = 0; off < n; off += gc.rows) {
+        const uint32_t m = std::min(gc.rows, n - off);
+        gc.draw(off, m);
+        HIPCHK(hipStreamSynchronize(ctx->st));
+        ctx->cfg.precision == SBMF_F32 ? fetch(float{}, off, m) : fetch(double{}, off, m);
+    }
+    API_END(ctx)
+}
+
+int sbmf_samples_foldin_scores(sbmf_ctx* ctx, uint32_t len, const uint32_t* items, const double* ratings, uint32_t scans,
+                               uint32_t flags, double* mean, double* stdev) {
+    API_BEGIN
+    const char* fn = "sbmf_samples_foldin_scores";
+    if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
+    samples_scope(ctx, fn);
+    if (flags & ~2u) sbmf::fail(SBMF_E_ARG, "%s: unknown flags 0x%x (bit 1 = clamp)", fn, flags & ~2u);
+    const uint32_t ptr[2] = {0, len};
+    guests_ready(ctx, fn, 1, ptr, items, ratings, scans);
+    const SampleStore& ss = ctx->samples;
+    hipStream_t st = ctx->st;
+    const uint32_t J = ctx->J;
+    GuestCall gc(ctx, fn, 1, ptr, items, ratings, scans, true);
+    sbmf::DBuf d_out;
+    d_out.alloc((size_t)2 * J * sizeof(double));
+    double* d = d_out.as<double>();
+    gc.draw(0, 1);
+    gc.score(1, (flags & 2u) ? 1 : 0);
+    HIPCHK(sbmf::launch_watch_moments(gc.d_S1.as<double>(), gc.d_S2.as<double>(), J, (double)ss.count, d, d + J, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    API_END(ctx)
+}
+
+int sbmf_samples_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select) {
+    API_BEGIN
+    if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
+    samples_scope(ctx, "sbmf_samples_foldin_timing");
+    SampleStore& ss = ctx->samples;
+    if (!ss.cap) sbmf::fail(SBMF_E_STATE, "sbmf_samples_foldin_timing: no sample store registered (sbmf_keep_samples)");
+    samples_sync(ctx);
+    if (ms_draw) *ms_draw = ss.timed_gdraw ? sbmf::ev_ms(ss.gdr[0], ss.gdr[1]) : 0.0;
+    if (ms_score) *ms_score = ss.timed_gscore ? sbmf::ev_ms(ss.gsc[0], ss.gsc[1]) : 0.0;
+    if (ms_select) *ms_select = ss.timed_gselect ? sbmf::ev_ms(ss.gse[0], ss.gse[1]) : 0.0;
+    API_END(ctx)
+}
+
 int sbmf_test_samples_tune(sbmf_ctx* ctx, uint64_t budget_bytes, int unfused) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
     ctx->samples.budget = budget_bytes;
-    ctx->samples.unfused = unfused != 0;
+    ctx->samples.unfused = (unfused & 1) != 0;
+    ctx->samples.fused_draw = (unfused & 2) != 0;
     API_END(ctx)
 }
 

@@ -24,6 +24,9 @@
 // -samples_out / -samples_every / -samples_max keep thinned samples of the SBPMF chain and write them to a
 // file after the run (sbmf_keep_samples / sbmf_save_samples); -samples_in runs no sweep: it loads such a
 // file and serves -out and -recommend from it (sbmf_load_samples / sbmf_samples_predict / sbmf_samples_recommend).
+// -samples_hyper_out writes the samples' hyperparameters beside them; with -samples_hyper_in, -samples_guests /
+// -samples_recommend_guests / -samples_scans serve -recommend_guests' lists for guests named after the run
+// (sbmf_load_samples_hyper / sbmf_samples_foldin_recommend).
 // Differences, by design: -seed is honoured (libfm.cpp:124 ignores it); on
 // error the exit code is 1 (the reference prints "ERROR" and returns 0).
 #include <algorithm>
@@ -492,6 +495,19 @@ void register_flags(CmdLine& cl) {
                          "the clamped posterior-mean prediction of the -test pairs, writes -out from it and, with "
                          "-recommend / -rec_users, the top-N lists from the stored samples; the data, -dim, -precision "
                          "and -quirks must be those of the run that wrote the file");
+    // guests folded into the stored samples (sbmf_save_samples_hyper / sbmf_load_samples_hyper / sbmf_samples_foldin_recommend)
+    cl.reg("samples_hyper_out", "filename for output: the kept samples' hyperparameters, the companion file of -samples_out's "
+                                "that folding guests into the samples later needs [with -samples_out]");
+    cl.reg("samples_hyper_in", "filename of the -samples_hyper_out file written beside -samples_in's [with -samples_in]");
+    cl.reg("samples_guests", "filename in -rec_guests' format: users outside the training set, served from the stored "
+                             "samples [MANDATORY with -samples_recommend_guests]");
+    cl.reg("samples_recommend_guests", "filename for output: -recommend_guests' lines for the guests of -samples_guests, "
+                                       "drawn at every stored sample with no sweep run; needs -samples_in and "
+                                       "-samples_hyper_in; shares -rec_topn and -rec_risk; the unbiased quirk sets only; "
+                                       "-seed and -quirks must be those of the run that wrote the files to reproduce its "
+                                       "-recommend_guests numbers");
+    cl.reg("samples_scans", "coordinate scans of a guest's row per stored sample, 1..64; default=1 [with "
+                            "-samples_recommend_guests]");
     cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
                           "numbers non-decreasing");
 }
@@ -508,7 +524,10 @@ struct Options {
     std::vector<int> dim;
     sbmf_config cfg;
     ListOpt users, guests, queries;
+    ListOpt sguests;  // -samples_recommend_guests / -samples_guests: the guests' list from the stored samples
     std::string samples_out, samples_in;  // the sample store: written after the run | served from, without one
+    std::string samples_hyper_out, samples_hyper_in;  // its hyperparameters' companion file
+    long samples_scans = 1;
     long samples_every = 1, samples_max = 0;  // (0: every kept sweep of the run)
     long topn = 10;  // -rec_topn and -rec_risk, shared by the three
     double risk = 0.0;
@@ -523,6 +542,8 @@ const char* const task_refusal = "only -task r (regression) is supported by the 
 const char* const rec_refusal = "-recommend is offered by the SBPMF sampler (-method mcmc -order sbpmf)";
 const char* const recg_refusal = "-recommend_guests is offered by the SBPMF sampler (-method mcmc -order sbpmf) with "
                                  "the unbiased quirk sets (final, sbpmf2, none)";
+const char* const sguests_refusal = "-samples_recommend_guests is offered for samples of the unbiased quirk sets (final, "
+                                    "sbpmf2, none): a guest bias would need a draw of its own";
 const char* const samples_refusal = "-samples_out / -samples_in are offered by the SBPMF sampler (-method mcmc -order sbpmf)";
 const char* const recq_refusal = "-recommend_queries is offered by libFM's MCMC / ALS learner (-method mcmc -order libfm, "
                                  "-method als) with -relation: it ranks the block rows of one relation";
@@ -567,12 +588,14 @@ void resolve_flags(const CmdLine& cl, Options& o) {
         if (o.rec_rel == o.rel_stems.size())
             fail("-rec_relation " + rec_relation + " names none of -relation's stems (" + o.relation + ")");
     }
-    if (!rec.on && !recg.on && !recq.on && (cl.has("rec_topn") || cl.has("rec_risk")))
+    ListOpt& sg = o.sguests;
+    sg = {cl.has("samples_recommend_guests"), cl.get("samples_guests", ""), cl.get("samples_recommend_guests", "")};
+    if (!rec.on && !recg.on && !recq.on && !sg.on && (cl.has("rec_topn") || cl.has("rec_risk")))
         fail("-rec_users / -rec_topn / -rec_risk go with -recommend");
     if (rec.on && o.method != "mcmc") fail(rec_refusal);  // before any file is opened
     if (recg.on && o.method != "mcmc") fail(recg_refusal);
     o.topn = cl.getl("rec_topn", 10);
-    if ((rec.on || recg.on || recq.on) && (o.topn < 1 || o.topn > 1024)) fail("-rec_topn must be in 1..1024");
+    if ((rec.on || recg.on || recq.on || sg.on) && (o.topn < 1 || o.topn > 1024)) fail("-rec_topn must be in 1..1024");
     o.risk = cl.getd("rec_risk", 0.0);
     o.exclude = cl.get("rec_exclude", "");
     o.fmt = cl.get("format", "auto");
@@ -592,6 +615,22 @@ void resolve_flags(const CmdLine& cl, Options& o) {
     o.samples_max = cl.getl("samples_max", 0);
     if (cl.has("samples_every") && o.samples_every < 1) fail("-samples_every must be at least 1");
     if (cl.has("samples_max") && (o.samples_max < 1 || o.samples_max > 65535)) fail("-samples_max must be in 1..65535");
+    // guests from the stored samples: each flag with its partner
+    o.samples_hyper_out = cl.get("samples_hyper_out", "");
+    o.samples_hyper_in = cl.get("samples_hyper_in", "");
+    if (cl.has("samples_hyper_out") && o.samples_hyper_out.empty()) fail("-samples_hyper_out needs a file name");
+    if (cl.has("samples_hyper_in") && o.samples_hyper_in.empty()) fail("-samples_hyper_in needs a file name");
+    if (cl.has("samples_hyper_out") && !cl.has("samples_out")) fail("-samples_hyper_out goes with -samples_out <file>");
+    if (cl.has("samples_hyper_in") && !cl.has("samples_in")) fail("-samples_hyper_in goes with -samples_in <file>");
+    if (sg.on && sg.out.empty()) fail("-samples_recommend_guests needs a file name");
+    if (!sg.on && cl.has("samples_guests")) fail("-samples_guests goes with -samples_recommend_guests <file>");
+    if (!sg.on && cl.has("samples_scans")) fail("-samples_scans goes with -samples_recommend_guests <file>");
+    if (sg.on && !cl.has("samples_in")) fail("-samples_recommend_guests goes with -samples_in <file>");
+    if (sg.on && !cl.has("samples_hyper_in"))
+        fail("-samples_recommend_guests needs -samples_hyper_in <file> (the samples' hyperparameters, written by -samples_hyper_out)");
+    if (sg.on && sg.in.empty()) fail("-samples_recommend_guests needs -samples_guests <file> ('guest item rating' per line)");
+    o.samples_scans = cl.getl("samples_scans", 1);
+    if (cl.has("samples_scans") && (o.samples_scans < 1 || o.samples_scans > 64)) fail("-samples_scans must be in 1..64");
 }
 
 // Step 2: what also depends on the kind of input, for which -format auto looks into the train file (the first
@@ -623,6 +662,7 @@ void resolve_learner(const CmdLine& cl, Options& o) {
     if (o.queries.on && !o.lfm) fail(recq_refusal);
     if (o.guests.on && (o.lfm || o.biased)) fail(recg_refusal);  // (a guest bias would need its own draw)
     if ((!o.samples_out.empty() || !o.samples_in.empty()) && o.lfm) fail(samples_refusal);
+    if (o.sguests.on && o.biased) fail(sguests_refusal);
     if (o.method != "mcmc" && !o.vb && !o.als) fail("-method " + o.method + " is not supported (use mcmc, als or vb)");
     if (!cl.has("train") || !cl.has("test")) fail("-train and -test are mandatory");
     const std::vector<int>& dim = o.dim = split_ints(cl.get("dim", "1,1,8"));
@@ -711,7 +751,7 @@ struct HostData {
     std::vector<double> greg_w, greg_v;
     std::vector<RelFiles> rels;
     std::vector<uint32_t> rec_ids;  // -rec_users
-    Grouped guests;                 // -rec_guests as a CSR of items, item ids as the sampler's, and their ratings
+    Grouped guests;                 // -rec_guests (or -samples_guests) as a CSR of items, item ids as the sampler's, and their ratings
     std::vector<double> g_ratings;
     // the queries: their main features, a block row of every relation but the candidates', the exclusions
     sbmf_cases qcases{};
@@ -748,7 +788,7 @@ void load_data(Options& o, HostData& d) {
     if (d.general) {
         // refused before any learning: only libFM's own chain is defined on such cases
         const char* why =
-            o.users.on || o.guests.on ? "-recommend / -recommend_guests rank the items of the SBPMF sampler's user x item model"
+            o.users.on || o.guests.on || o.sguests.on ? "-recommend / -recommend_guests rank the items of the SBPMF sampler's user x item model"
             : o.vb                    ? "-method vb (online VB) updates one user and one item attribute per case"
             : !o.lfm                  ? "-order sbpmf (the SBPMF sampler) factorizes a user x item rating matrix"
                                       : nullptr;
@@ -769,7 +809,7 @@ void load_data(Options& o, HostData& d) {
     // = max feature id + 1 (:328).  With one user and one item feature per line that is the users-first layout with
     // item offset num_user, so no flag is needed (-item_offset overrides it).
     // (-recommend needs to know which ids are items, so it takes that split for the SBPMF sampler too)
-    if ((o.lfm || o.vb || o.users.on || o.guests.on) && o.libfm_input && !o.has_item_offset && !d.general)
+    if ((o.lfm || o.vb || o.users.on || o.guests.on || o.sguests.on) && o.libfm_input && !o.has_item_offset && !d.general)
         d.off = users_first_offset(d.tr, d.te);
     d.ioff = o.libfm_input ? d.off : 0;
     // -meta and -regular (libFM's learners): one group id per attribute of num_attribute = the
@@ -812,20 +852,23 @@ void load_data(Options& o, HostData& d) {
 void load_lists(const Options& o, HostData& d) {
     if (o.users.on) d.rec_ids = read_ids(o.users.in, "-rec_users", "user id");
     if (o.users.on && d.rec_ids.empty()) fail("-rec_users: " + o.users.in + " lists no user");
-    if (o.guests.on) {
+    // (-recommend_guests and -samples_recommend_guests never meet: the second goes with -samples_in)
+    const ListOpt& gl = o.sguests.on ? o.sguests : o.guests;
+    if (gl.on) {
+        const std::string flag = o.sguests.on ? "-samples_guests" : "-rec_guests";
         unsigned long long it = 0;
         double r = 0.0;
         d.guests = read_grouped(
-            o.guests.in, "-rec_guests", "guest item rating", "guest",
+            gl.in, flag.c_str(), "guest item rating", "guest",
             [&](const char* s, const std::string&, unsigned long long& g) {
                 return std::sscanf(s, "%llu %llu %lf", &g, &it, &r) == 3 && g <= 0xfffffffdull;
             },
             [&](const std::string& line) {
-                if (it < d.ioff || it - d.ioff > 0xfffffffeull) fail("-rec_guests: item id out of range in '" + line + "'");
+                if (it < d.ioff || it - d.ioff > 0xfffffffeull) fail(flag + ": item id out of range in '" + line + "'");
                 d.g_ratings.push_back(r);
                 return (uint32_t)(it - d.ioff);
             });
-        if (d.guests.ptr.size() < 2) fail("-rec_guests: " + o.guests.in + " lists no guest");
+        if (d.guests.ptr.size() < 2) fail(flag + ": " + gl.in + " lists no guest");
     }
     if (!o.queries.on) return;
     if (sbmf_load_libfm_cases(o.queries.in.c_str(), &d.qcases) != SBMF_OK) fail(std::string("-rec_queries: ") + sbmf_loader_error());
@@ -955,6 +998,7 @@ void run(sbmf_ctx* ctx, const Options& o, const HostData& d) {
     }
     chk(ctx, sbmf_run(ctx, cfg.num_iter + cfg.burnin, on_sweep, &rs));
     if (!o.samples_out.empty()) chk(ctx, sbmf_save_samples(ctx, o.samples_out.c_str()));
+    if (!o.samples_hyper_out.empty()) chk(ctx, sbmf_save_samples_hyper(ctx, o.samples_hyper_out.c_str()));
 }
 
 // One top-N file: `recommend` fills topn slots per row of its list; every filled slot is a line
@@ -995,9 +1039,11 @@ void write_outputs(sbmf_ctx* ctx, const Options& o, const HostData& d) {
 }
 
 // -samples_in: no sweep.  The stored samples' clamped posterior-mean prediction of the test pairs, its RMSE on
-// the "#Samples=" line, -out from it, and -recommend's lists from the store through the top-N writer.
+// the "#Samples=" line, -out from it, and -recommend's lists from the store through the top-N writer; with
+// -samples_hyper_in the guests' lists too.
 void serve_samples(sbmf_ctx* ctx, const Options& o, const HostData& d) {
     chk(ctx, sbmf_load_samples(ctx, o.samples_in.c_str()));
+    if (!o.samples_hyper_in.empty()) chk(ctx, sbmf_load_samples_hyper(ctx, o.samples_hyper_in.c_str()));
     uint32_t count = 0;
     chk(ctx, sbmf_samples_info(ctx, &count, nullptr, nullptr, nullptr));
     const uint64_t n = d.te.n;
@@ -1013,6 +1059,13 @@ void serve_samples(sbmf_ctx* ctx, const Options& o, const HostData& d) {
         write_topn(ctx, [&](sbmf_ctx* c, uint32_t topn, uint32_t flags, double risk, uint32_t* it, double* mean, double* sd) {
             return sbmf_samples_recommend(c, nu, ids, topn, flags, risk, it, mean, sd);
         }, o, o.users.out, d.rec_ids.size(), ids, d.ioff);
+    }
+    if (o.sguests.on) {
+        const uint32_t ng = (uint32_t)d.guests.ptr.size() - 1, scans = (uint32_t)o.samples_scans;
+        write_topn(ctx, [&](sbmf_ctx* c, uint32_t topn, uint32_t flags, double risk, uint32_t* it, double* mean, double* sd) {
+            return sbmf_samples_foldin_recommend(c, ng, d.guests.ptr.data(), d.guests.val.data(), d.g_ratings.data(), scans,
+                                                 topn, flags, risk, it, mean, sd);
+        }, o, o.sguests.out, ng, nullptr, d.ioff);
     }
     if (!o.out.empty()) {
         std::ofstream out(o.out);

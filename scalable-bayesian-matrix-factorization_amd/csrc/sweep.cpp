@@ -746,7 +746,7 @@ struct SweepRun {
             HIPCHK(hipEventRecord(c->wev[1], se));
         }
         // the sample store's copy of this sample (reads what the watch list reads)
-        if (c->samples.cap && collect) c->samples.keep<T>(c, hy.b0, se);
+        if (c->samples.cap && collect) c->samples.keep<T>(c, hy, se);
         // the fold-in list: every guest's row drawn from this sweep's V and the user half's
         // hyperparameters (the host's values: this sweep's, whatever d_hyper holds by now),
         // then, on a collected sweep, the guests' scores of this sample

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "samples_file_info", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "samples_file_info", "samples_hyper_file_info", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -331,6 +331,26 @@ def libfm_users_first(train, test=None):
                              % (int(np.min(d.item)), I - 1))
     rebase = lambda d: None if d is None else Data(d.user, np.asarray(d.item, np.int64) - I, d.rating)
     return rebase(train), rebase(test), I
+
+
+def _guest_csr(guests):
+    """(n, ptr, items, ratings) of guests given as a list of (items, ratings) pairs or as a CSR
+    tuple (ptr, items, ratings) of three 1-D numpy arrays."""
+    if isinstance(guests, tuple) and len(guests) == 3 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in guests):
+        ptr, items, ratings = _u32(guests[0]), _u32(guests[1]), _f64(guests[2])
+    else:
+        ptr = np.zeros(len(guests) + 1, dtype=np.int64)
+        for g, (it, _) in enumerate(guests):
+            ptr[g + 1] = ptr[g] + len(it)
+        ptr = _u32(ptr)
+        items = _u32(np.concatenate([np.asarray(it, dtype=np.int64).ravel() for it, _ in guests] + [np.zeros(0, np.int64)]))
+        ratings = _f64(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for _, r in guests] + [np.zeros(0)]))
+        if len(items) != len(ratings):
+            raise ValueError("a guest's items and ratings differ in length")
+    n = max(len(ptr) - 1, 0)
+    if n == 0:
+        ptr = np.zeros(1, np.uint32)
+    return n, ptr, items, ratings
 
 
 def config_default():
@@ -723,6 +743,69 @@ class FMLearnSBPMF:
         precision and quirk-set bias-ness; no sweep needed)."""
         self._check(lib.sbmf_load_samples(self.ctx, str(path).encode()))
 
+    # -- guests folded into the stored samples after the run (no sweep; also from files)
+    def sample_hyper(self, s):
+        """The hyperparameters of stored sample ``s`` (0 the oldest), as ``hyper()`` returns the chain's."""
+        K = self.cfg.num_factor
+        h = np.zeros(4 * K)
+        tau = C.c_double()
+        self._check(lib.sbmf_get_sample_hyper(self.ctx, int(s), _ptr(h, C.c_double), C.byref(tau)))
+        return {"sigma_u": h[:K], "mu_u": h[K:2 * K], "sigma_v": h[2 * K:3 * K], "mu_v": h[3 * K:], "tau": tau.value}
+
+    def save_samples_hyper(self, path):
+        """The samples' hyperparameters to the companion file of ``save_samples``' file."""
+        self._check(lib.sbmf_save_samples_hyper(self.ctx, str(path).encode()))
+
+    def load_samples_hyper(self, path):
+        """The companion file's hyperparameters for the samples ``load_samples`` loaded."""
+        self._check(lib.sbmf_load_samples_hyper(self.ctx, str(path).encode()))
+
+    def samples_foldin_recommend(self, guests, topn=10, exclude_rated=True, risk=0.0, clamp=False, scans=1):
+        """``foldin_recommend`` from the stored samples for guests named now (the form ``foldin``
+        takes): (items int64 [n, topn] with -1 in empty slots, mean, stdev).  ``scans``: coordinate
+        scans per sample (sbmf_samples_foldin_recommend)."""
+        n, ptr, items, ratings = _guest_csr(guests)
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        t = int(topn)
+        out = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(out.shape, np.nan), np.full(out.shape, np.nan)
+        flags = (0 if exclude_rated else 1) | (2 if clamp else 0)
+        self._check(lib.sbmf_samples_foldin_recommend(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                                                      _ptr(ratings, C.c_double), int(scans), t, flags, float(risk),
+                                                      _ptr(out, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = out[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def samples_foldin_rows(self, guests, scans=1):
+        """The guests' factor rows at every stored sample, [count, n, K], oldest sample first."""
+        n, ptr, items, ratings = _guest_csr(guests)
+        count = self.samples_info()["count"]
+        rows = np.zeros((max(count, 1), max(n, 1), self.cfg.num_factor))  # (n = 0: nothing is written)
+        self._check(lib.sbmf_samples_foldin_rows(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                                                 _ptr(ratings, C.c_double), int(scans), _ptr(rows, C.c_double)))
+        return rows[:count, :n]
+
+    def samples_foldin_scores(self, items, ratings, clamp=False, scans=1):
+        """(mean, stdev) of one guest's score of every item over the stored samples (the guest is
+        drawn as guest 0 of a list)."""
+        items, ratings = _u32(np.asarray(items, dtype=np.int64).ravel()), _f64(np.asarray(ratings, dtype=np.float64).ravel())
+        if len(items) != len(ratings):
+            raise ValueError("items and ratings differ in length")
+        _, ni, _, _ = self.dims()
+        mean, sd = np.zeros(ni), np.zeros(ni)
+        self._check(lib.sbmf_samples_foldin_scores(self.ctx, len(items), _ptr(items, C.c_uint32), _ptr(ratings, C.c_double),
+                                                   int(scans), 2 if clamp else 0, _ptr(mean, C.c_double),
+                                                   _ptr(sd, C.c_double)))
+        return mean, sd
+
+    def samples_foldin_timing(self):
+        """Device ms of the last guest call's draw, scoring launch and selection (its last slice)."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(lib.sbmf_samples_foldin_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"ms_draw": a.value, "ms_score": b.value, "ms_select": c.value}
+
     # -- posterior top-N for guests: users outside the training set, given by their ratings
     def foldin(self, guests, clamp=False):
         """Register a fold-in list (sbmf_foldin_users): ``guests`` is a list of
@@ -730,20 +813,7 @@ class FMLearnSBPMF:
         (ptr, items, ratings) of three 1-D numpy arrays.  From the next sweep on every guest's
         factor row is drawn beside the chain and its scores accumulated on collected
         sweeps.  An empty list drops the fold-in list and frees its device buffers."""
-        if isinstance(guests, tuple) and len(guests) == 3 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in guests):
-            ptr, items, ratings = _u32(guests[0]), _u32(guests[1]), _f64(guests[2])
-        else:
-            ptr = np.zeros(len(guests) + 1, dtype=np.int64)
-            for g, (it, _) in enumerate(guests):
-                ptr[g + 1] = ptr[g] + len(it)
-            ptr = _u32(ptr)
-            items = _u32(np.concatenate([np.asarray(it, dtype=np.int64).ravel() for it, _ in guests] + [np.zeros(0, np.int64)]))
-            ratings = _f64(np.concatenate([np.asarray(r, dtype=np.float64).ravel() for _, r in guests] + [np.zeros(0)]))
-            if len(items) != len(ratings):
-                raise ValueError("a guest's items and ratings differ in length")
-        n = max(len(ptr) - 1, 0)
-        if n == 0:
-            ptr = np.zeros(1, np.uint32)
+        n, ptr, items, ratings = _guest_csr(guests)
         self._check(lib.sbmf_foldin_users(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
                                           _ptr(ratings, C.c_double), 1 if clamp else 0))
         self._n_guests = n
@@ -888,6 +958,19 @@ def samples_file_info(path):
     out = {k: x.value for k, x in zip(keys, v)}
     out["precision"] = "f32" if out["precision"] == F32 else "f64"
     out["bias"] = bool(out["bias"])
+    out["bytes"] = b.value
+    return out
+
+
+def samples_hyper_file_info(path):
+    """sbmf_samples_hyper_file_info: the header of a sample file's companion file, validated against
+    the file's size (no GPU): {"version", "num_factor", "count", "bytes"}."""
+    v = [C.c_uint32() for _ in range(3)]
+    b = C.c_uint64()
+    rc = lib.sbmf_samples_hyper_file_info(str(path).encode(), *[C.byref(x) for x in v], C.byref(b))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    out = {k: x.value for k, x in zip(("version", "num_factor", "count"), v)}
     out["bytes"] = b.value
     return out
 

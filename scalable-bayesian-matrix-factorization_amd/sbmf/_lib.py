@@ -131,6 +131,16 @@ SIGNATURES = {
     "sbmf_load_samples": (C.c_int, [C.c_void_p, C.c_char_p]),
     "sbmf_samples_file_info": (C.c_int, [C.c_char_p, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32, _P_U32,
                                          C.POINTER(C.c_uint64)]),
+    "sbmf_get_sample_hyper": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_save_samples_hyper": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_load_samples_hyper": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_samples_hyper_file_info": (C.c_int, [C.c_char_p, _P_U32, _P_U32, _P_U32, C.POINTER(C.c_uint64)]),
+    "sbmf_samples_foldin_recommend": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_U32, _P_F64, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
+    "sbmf_samples_foldin_rows": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_U32, _P_F64, C.c_uint32, _P_F64]),
+    "sbmf_samples_foldin_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_F64, C.c_uint32, C.c_uint32, _P_F64,
+                                             _P_F64]),
+    "sbmf_samples_foldin_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64]),
     "sbmf_fm_query_cases": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CasesC), C.POINTER(_P_U32), _P_U32, _P_U32,
                                       C.c_uint32]),
     "sbmf_fm_query_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
