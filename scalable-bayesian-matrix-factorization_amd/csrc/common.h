@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -62,6 +63,30 @@ inline void event_destroy(hipEvent_t& e) {
     audit().events--;
     e = nullptr;
 }
+inline double ev_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return NAN;
+    return ms;
+}
+// A [begin, end] event pair around the last run of some device work; `timed`: it ran at least once
+// since the pair was created (the events of a pair never recorded cannot be read).
+struct Span {
+    hipEvent_t ev[2] = {};
+    bool timed = false;
+    void create() {
+        for (hipEvent_t& e : ev) event_create(&e);
+    }
+    void destroy() {
+        for (hipEvent_t& e : ev) event_destroy(e);
+        timed = false;
+    }
+    void begin(hipStream_t st) { HIPCHK(hipEventRecord(ev[0], st)); }
+    void end(hipStream_t st) {
+        HIPCHK(hipEventRecord(ev[1], st));
+        timed = true;
+    }
+    double ms() const { return timed ? ev_ms(ev[0], ev[1]) : 0.0; }  // (the caller has synchronised)
+};
 // pinned host memory: the byte count is kept by the caller (freed with the same size)
 inline void pinned_alloc(void** p, size_t bytes) {
     HIPCHK(hipHostMalloc(p, bytes, hipHostMallocDefault));

@@ -1,5 +1,6 @@
-// ctx.h -- what the host runtime's files (prepare.cpp, sweep.cpp, lists.cpp, sbmf.cpp) share: the
-// row layout of one orientation, the hyperparameter state, the score lists and the context.
+// ctx.h -- what the host runtime's files (prepare.cpp, sweep.cpp, lists.cpp, samples.cpp,
+// samples_file.cpp, sbmf.cpp) share: the row layout of one orientation, the hyperparameter state, the
+// score lists, the sample store and the context (lists.h: what the lists and the store share).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,7 @@
 #include "fmg.h"
 #include "fmq.h"
 #include "foldin.h"
+#include "lists.h"
 #include "recommend.h"
 #include "samples.h"
 #include "samples_foldin.h"
@@ -112,8 +114,7 @@ struct ScoreList {
     int clamp = 0;         // flags bit 0: scores clamped like the test prediction
     bool latest = false;   // the sums hold one sample, the latest (ALS): the spread reads back as exactly 0
     DBuf d_ids, d_S1, d_S2;  // the rows' indices in their table (the watched users, or 0..n-1); the sums
-    hipEvent_t sel[2] = {};  // the last selection [begin, end]
-    bool timed_select = false;
+    Span sel;  // the last selection
     void alloc(uint32_t n_, uint32_t J_, int clamp_, hipStream_t st);  // sums zeroed; d_ids is the caller's to fill
     void drop();
     template <typename T>
@@ -140,11 +141,8 @@ struct SampleStore {
     std::vector<uint32_t> sweep;  // [cap], by slot
     std::vector<double> hyper;    // [cap][4 K + 1], by slot: sbmf_get_hyper's block, then tau
     bool has_hyper = false;       // every kept sample's entry of `hyper` is its sweep's
-    hipEvent_t cev[2] = {}, scv[2] = {}, sel[2] = {};  // the last copy, scoring and selection [begin, end]
-    bool timed_copy = false, timed_score = false, timed_select = false;
-    // the last guest call (sbmf_samples_foldin_*): its draw, scoring and selection [begin, end]
-    hipEvent_t gdr[2] = {}, gsc[2] = {}, gse[2] = {};
-    bool timed_gdraw = false, timed_gscore = false, timed_gselect = false;
+    Span cev, scv, sel;  // the last copy, scoring and selection
+    Span gdr, gsc, gse;  // the last guest call (sbmf_samples_foldin_*): its draw, scoring and selection
     // test hook (sbmf_test_samples_tune): the temporaries' budget in bytes (0: the default) and
     // the per-sample loop of launch_watch_accum in the fused kernel's place; and the guests' draw
     // by the one fused launch in place of the default, one launch per sample and scan
@@ -278,17 +276,18 @@ struct sbmf_ctx {
     // Watch list (sbmf_watch_users): the watched users' scores, from U and the biases
     ScoreList watch{"watch list", "sbmf_watch_users"};
     hipEvent_t wev[2] = {};  // the last scoring launch [begin, end] (recorded once watch.count > 0)
-    // Fold-in list (sbmf_foldin_users): guests given by their ratings (a CSR on the device),
+    // Fold-in list (sbmf_foldin_users): guests given by their ratings (fcsr: the CSR on the device),
     // their factor rows G [n + 2][Kp] in the tables' type (row n zero, row n + 1 slack: the
     // tables' layout, so the watch list's scoring kernel reads it as a U), drawn after every
     // sweep's item half (foldin.hip), and the moments of their scores as the watch
     // list keeps them.  d_fhyp is the list's own [sig_u | mu_u] (2 Kp doubles) of the sweep
     // being evaluated: d_hyper may already hold the next sweep's (stage_hyper).  guests.d_ids is
-    // 0..n-1 (the scoring kernel's user list), d_forder the guests by falling length.  Nothing
-    // here exists while no list is registered.
+    // 0..n-1 (the scoring kernel's user list; fcsr.d_ids stays empty), fcsr.d_order the guests by
+    // falling length.  Nothing here exists while no list is registered.
     ScoreList guests{"fold-in list", "sbmf_foldin_users"};
     uint32_t fdrawn = 0;   // sweeps drawn since the list was registered (guests.count: the collected ones)
-    DBuf d_fptr, d_fitems, d_fratings, d_forder, d_fG, d_fE, d_fhyp;
+    GuestCSR fcsr;
+    DBuf d_fG, d_fhyp;
     double* h_fhyp = nullptr;  // pinned staging of d_fhyp
     size_t h_fhyp_bytes = 0;
     // hyper copy done = draw begin, draw end = scoring begin (recorded once fdrawn > 0), scoring
@@ -337,6 +336,10 @@ namespace sbmf {
 
 // what the runtime's files use of each other (the templates: instantiated for float and double)
 int api_error(sbmf_ctx* ctx);
+// the sample store (samples.cpp), for its files (samples_file.cpp): in scope, a sample kept, its
+// queued copies done; the device bytes of one slot
+void samples_ready(sbmf_ctx* c, const char* fn);
+size_t slot_bytes(const sbmf_ctx* c);
 void partition_bounds(const uint32_t* ptr, uint32_t R, int nranks, uint64_t* bounds);
 template <typename T>
 void prepare_T(sbmf_ctx* c);
@@ -390,12 +393,6 @@ static void ensure_pinned(sbmf_ctx* c, size_t bytes) {
     c->h_pinned_bytes = 0;
     pinned_alloc((void**)&c->h_pinned, bytes);
     c->h_pinned_bytes = bytes;
-}
-
-static double ev_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return NAN;
-    return ms;
 }
 
 }  // namespace sbmf

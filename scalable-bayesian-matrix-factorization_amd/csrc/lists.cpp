@@ -1,7 +1,114 @@
 // lists.cpp -- the score lists (ScoreList, ctx.h) and their entry points: the watch list
 // (sbmf_watch_*, sbmf_recommend), the fold-in list (sbmf_foldin_*) and the libFM learner's query
-// list (sbmf_fm_query_*, fmq.h).
+// list (sbmf_fm_query_*, fmq.h); and what they share with the sample store (lists.h): the scope
+// check, the top-N selection, one row's moments and the guests' CSR.
 #include "ctx.h"
+
+namespace sbmf {
+
+// one real rank (`what`: the feature's noun), then prepared: two of the checks every scope makes
+static void one_real_rank(const sbmf_ctx* c, const char* what, const char* fn) {
+    if (c->virt) fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no %s there", fn, what);
+    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
+        fail(SBMF_E_STATE, "%s: the %s runs on one rank; this context joined a communicator", fn, what);
+}
+static void is_prepared(const sbmf_ctx* c, const char* fn) {
+    if (!c->prepared) fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+}
+void list_scope(const sbmf_ctx* c, const char* what, const char* fn, bool unbiased_only) {
+    if (c->cfg.method != SBMF_METHOD_MCMC)
+        fail(SBMF_E_STATE, "%s: the %s is offered by the SBPMF sampler (SBMF_METHOD_MCMC) only; this "
+                           "context runs the %s learner", fn, what,
+             c->cfg.method == SBMF_METHOD_VB ? "online VB" : c->cfg.method == SBMF_METHOD_ALS ? "ALS" : "libFM MCMC");
+    if (unbiased_only && c->bias)
+        fail(SBMF_E_STATE, "%s: the %s covers the unbiased quirk sets (final, sbpmf2, none); a guest of "
+                           "the biased sampler (bias2 / bias22) would need a bias draw of its own", fn, what);
+    one_real_rank(c, what, fn);
+    is_prepared(c, fn);
+}
+void list_sync(sbmf_ctx* c) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->sto));
+    HIPCHK(hipStreamSynchronize(c->st));
+}
+
+void TopnScratch::alloc(uint32_t rows, uint32_t topn, uint32_t J, bool exclude) {
+    const size_t slots = (size_t)rows * topn;
+    d_it.alloc(slots * sizeof(uint32_t));
+    d_ms.alloc(2 * slots * sizeof(double));
+    if (exclude) d_mask.alloc((size_t)rows * watch_jw(J) * sizeof(uint32_t));
+}
+void select_topn(TopnScratch& t, const uint32_t* d_ids, uint32_t m, const double* S1, const double* S2, uint32_t J,
+                 uint32_t count, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn, double risk, Span& span,
+                 hipStream_t st, uint32_t* items, double* mean, double* stdev) {
+    const uint32_t Jw = watch_jw(J);
+    const size_t slots = (size_t)m * topn;
+    uint32_t* mask = csr_ptr ? t.d_mask.as<uint32_t>() : nullptr;
+    double* ms = t.d_ms.as<double>();
+    span.begin(st);
+    if (mask) {
+        HIPCHK(hipMemsetAsync(mask, 0, (size_t)m * Jw * sizeof(uint32_t), st));
+        HIPCHK(launch_watch_mask(d_ids, m, csr_ptr, csr_items, mask, Jw, st));
+    }
+    HIPCHK(launch_watch_select(m, S1, S2, J, (double)count, risk, mask, topn, t.d_it.as<uint32_t>(), ms, ms + slots, st));
+    span.end(st);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(items, t.d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mean, ms, slots * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, ms + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+}
+void row_moments(const double* S1, const double* S2, uint32_t J, uint32_t count, hipStream_t st, double* mean, double* stdev) {
+    DBuf tmp;
+    tmp.alloc((size_t)2 * J * sizeof(double));
+    double* d = tmp.as<double>();
+    HIPCHK(launch_watch_moments(S1, S2, J, (double)count, d, d + J, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+void GuestCSR::check(const char* fn, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings, uint32_t J) {
+    if (n && !ptr) fail(SBMF_E_ARG, "%s: null ptr with n > 0", fn);
+    if (n >= 0xfffffffeu) fail(SBMF_E_ARG, "%s: %u guests are too many", fn, n);
+    for (uint32_t g = 0; g < n; ++g)
+        if (ptr[g + 1] < ptr[g]) fail(SBMF_E_ARG, "%s: ptr decreases at guest %u (%u then %u)", fn, g, ptr[g], ptr[g + 1]);
+    const uint32_t p0 = n ? ptr[0] : 0, nnz = n ? ptr[n] - p0 : 0;
+    if (nnz && (!items || !ratings)) fail(SBMF_E_ARG, "%s: null items / ratings with ratings listed", fn);
+    for (uint32_t q = 0; q < nnz; ++q)
+        if (items[p0 + q] >= J)
+            fail(SBMF_E_ARG, "%s: items[%u] = %u is not below the %u items", fn, p0 + q, items[p0 + q], J);
+}
+void GuestCSR::upload(uint32_t n_, const uint32_t* ptr, const uint32_t* items, const double* ratings, uint32_t rows_per_slice,
+                      hipStream_t st, uint32_t* ids) {
+    n = n_;
+    const uint32_t p0 = ptr[0];
+    nnz = ptr[n] - p0;
+    std::vector<uint32_t> hp(n + 1), ident(n);
+    for (uint32_t g = 0; g <= n; ++g) hp[g] = ptr[g] - p0;  // the device CSR starts at 0
+    std::iota(ident.begin(), ident.end(), 0u);
+    std::vector<uint32_t> order(ident);
+    for (uint32_t off = 0; off < n; off += rows_per_slice)
+        std::stable_sort(order.begin() + off, order.begin() + std::min(n, off + rows_per_slice),
+                         [&](uint32_t x, uint32_t y) { return hp[x + 1] - hp[x] > hp[y + 1] - hp[y]; });
+    d_E.alloc((size_t)nnz * sizeof(double));
+    d_items.alloc((size_t)nnz * sizeof(uint32_t));
+    d_ratings.alloc((size_t)nnz * sizeof(double));
+    sbmf::upload(d_ptr, hp, st);
+    sbmf::upload(d_order, order, st);
+    if (ids) HIPCHK(hipMemcpyAsync(ids, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    else sbmf::upload(d_ids, ident, st);
+    if (nnz) {
+        HIPCHK(hipMemcpyAsync(d_items.p, items + p0, (size_t)nnz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_ratings.p, ratings + p0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // the vectors are locals
+}
+void GuestCSR::drop() {
+    for (DBuf* d : {&d_ptr, &d_items, &d_ratings, &d_order, &d_E, &d_ids}) d->release();
+    n = nnz = 0;
+}
+
+}  // namespace sbmf
 
 void ScoreList::alloc(uint32_t n_, uint32_t J_, int clamp_, hipStream_t st) {
     n = n_;
@@ -12,17 +119,16 @@ void ScoreList::alloc(uint32_t n_, uint32_t J_, int clamp_, hipStream_t st) {
     d_S1.alloc(bytes);
     d_S2.alloc(bytes);
     d_ids.alloc((size_t)n * sizeof(uint32_t));
-    for (hipEvent_t& e : sel) sbmf::event_create(&e);
+    sel.create();
     HIPCHK(hipMemsetAsync(d_S1.p, 0, bytes, st));
     HIPCHK(hipMemsetAsync(d_S2.p, 0, bytes, st));
 }
 void ScoreList::drop() {
     for (sbmf::DBuf* d : {&d_ids, &d_S1, &d_S2}) d->release();
-    for (hipEvent_t& e : sel) sbmf::event_destroy(e);
+    sel.destroy();
     n = J = Jp = count = 0;
     clamp = 0;
     latest = false;
-    timed_select = false;
 }
 // this sample's scores of the list's rows of `rows` (a factor table: U, or the guests' G) against
 // every item, added to the sums; the caller records the events around it
@@ -37,70 +143,25 @@ template void ScoreList::accumulate<float>(sbmf_ctx*, const float*, const double
 template void ScoreList::accumulate<double>(sbmf_ctx*, const double*, const double*, const double*, double, hipStream_t);
 void ScoreList::scores(sbmf_ctx* c, const char* fn, uint32_t row, double* mean, double* stdev) {
     if (row >= n) sbmf::fail(SBMF_E_ARG, "%s: row %u of a %s of %u", fn, row, what, n);
-    sbmf::DBuf tmp;
-    tmp.alloc((size_t)2 * J * sizeof(double));
-    double* d = tmp.as<double>();
-    HIPCHK(sbmf::launch_watch_moments(d_S1.as<double>() + (size_t)row * Jp, d_S2.as<double>() + (size_t)row * Jp, J,
-                                      (double)count, d, d + J, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipMemcpy(mean, d, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
-    if (stdev) HIPCHK(hipMemcpy(stdev, d + J, (size_t)J * sizeof(double), hipMemcpyDeviceToHost));
+    sbmf::row_moments(d_S1.as<double>() + (size_t)row * Jp, d_S2.as<double>() + (size_t)row * Jp, J, count, c->st, mean, stdev);
     if (stdev && latest) std::fill(stdev, stdev + J, 0.0);
 }
 // top-N of every row; "rated" items (flags bit 0 clear: left out) are those of the rows' CSR --
 // the user side's for watched users, the guest CSR for guests
 void ScoreList::recommend(sbmf_ctx* c, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn,
                           uint32_t flags, double risk, uint32_t* items, double* mean, double* stdev) {
-    const uint32_t Jw = sbmf::watch_jw(J);
-    const size_t slots = (size_t)n * topn;
-    sbmf::DBuf d_it, d_ms, d_mask;
-    d_it.alloc(slots * sizeof(uint32_t));
-    d_ms.alloc(2 * slots * sizeof(double));
     const bool exclude = !(flags & 1u);
-    if (exclude) d_mask.alloc((size_t)n * Jw * sizeof(uint32_t));
-    hipStream_t st = c->st;
-    HIPCHK(hipEventRecord(sel[0], st));
-    if (exclude) {
-        HIPCHK(hipMemsetAsync(d_mask.p, 0, (size_t)n * Jw * sizeof(uint32_t), st));
-        HIPCHK(sbmf::launch_watch_mask(d_ids.as<uint32_t>(), n, csr_ptr, csr_items, d_mask.as<uint32_t>(), Jw, st));
-    }
-    HIPCHK(sbmf::launch_watch_select(n, d_S1.as<double>(), d_S2.as<double>(), J, (double)count, risk,
-                                     exclude ? d_mask.as<uint32_t>() : nullptr, topn, d_it.as<uint32_t>(),
-                                     d_ms.as<double>(), d_ms.as<double>() + slots, st));
-    HIPCHK(hipEventRecord(sel[1], st));
-    HIPCHK(hipStreamSynchronize(st));
-    timed_select = true;
-    HIPCHK(hipMemcpy(items, d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mean, d_ms.p, slots * sizeof(double), hipMemcpyDeviceToHost));
-    if (stdev) HIPCHK(hipMemcpy(stdev, d_ms.as<double>() + slots, slots * sizeof(double), hipMemcpyDeviceToHost));
+    sbmf::TopnScratch t;
+    t.alloc(n, topn, J, exclude);
+    sbmf::select_topn(t, d_ids.as<uint32_t>(), n, d_S1.as<double>(), d_S2.as<double>(), J, count, exclude ? csr_ptr : nullptr,
+                      csr_items, topn, risk, sel, c->st, items, mean, stdev);
     if (stdev && latest)  // one sample: no spread (the empty slots keep their NaN)
-        for (size_t q = 0; q < slots; ++q)
+        for (size_t q = 0, slots = (size_t)n * topn; q < slots; ++q)
             if (items[q] != 0xffffffffu) stdev[q] = 0.0;
 }
 
 extern "C" {
 
-// The learners and schedules a list covers; everything else is SBMF_E_STATE.
-static void list_scope(const sbmf_ctx* c, const ScoreList& l, const char* fn, bool unbiased_only) {
-    if (c->cfg.method != SBMF_METHOD_MCMC)
-        sbmf::fail(SBMF_E_STATE, "%s: the %s is offered by the SBPMF sampler (SBMF_METHOD_MCMC) only; this "
-                                 "context runs the %s learner", fn, l.what,
-                   c->cfg.method == SBMF_METHOD_VB ? "online VB" : c->cfg.method == SBMF_METHOD_ALS ? "ALS" : "libFM MCMC");
-    if (unbiased_only && c->bias)
-        sbmf::fail(SBMF_E_STATE, "%s: the %s covers the unbiased quirk sets (final, sbpmf2, none); a guest of "
-                                 "the biased sampler (bias2 / bias22) would need a bias draw of its own", fn, l.what);
-    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no %s there", fn, l.what);
-    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
-        sbmf::fail(SBMF_E_STATE, "%s: the %s runs on one rank; this context joined a communicator", fn, l.what);
-    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
-}
-// a list's queued work is done (it runs on the evaluation's stream, which the compute stream
-// waits for before the sweep's results are copied)
-static void list_sync(sbmf_ctx* c) {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    HIPCHK(hipStreamSynchronize(c->sto));
-    HIPCHK(hipStreamSynchronize(c->st));
-}
 static void list_registered(const ScoreList& l, const char* fn) {
     if (!l.n) sbmf::fail(SBMF_E_STATE, "%s: no %s registered (%s)", fn, l.what, l.reg);
 }
@@ -127,7 +188,7 @@ static void watch_drop(sbmf_ctx* c) {
 int sbmf_watch_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t flags) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
-    list_scope(ctx, ctx->watch, "sbmf_watch_users", false);
+    list_scope(ctx, ctx->watch.what, "sbmf_watch_users", false);
     if (n && !users) sbmf::fail(SBMF_E_ARG, "null user list with n > 0");
     if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_watch_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
     for (uint32_t w = 0; w < n; ++w)
@@ -151,7 +212,7 @@ int sbmf_watch_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t 
 int sbmf_watch_scores(sbmf_ctx* ctx, uint32_t w, double* mean, double* stdev) {
     API_BEGIN
     if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
-    list_scope(ctx, ctx->watch, "sbmf_watch_scores", false);
+    list_scope(ctx, ctx->watch.what, "sbmf_watch_scores", false);
     list_ready(ctx, ctx->watch, "sbmf_watch_scores");
     ctx->watch.scores(ctx, "sbmf_watch_scores", w, mean, stdev);
     API_END(ctx)
@@ -161,7 +222,7 @@ int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, ui
                    double* stdev) {
     API_BEGIN
     if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
-    list_scope(ctx, ctx->watch, "sbmf_recommend", false);
+    list_scope(ctx, ctx->watch.what, "sbmf_recommend", false);
     recommend_args("sbmf_recommend", topn, flags, risk);
     list_ready(ctx, ctx->watch, "sbmf_recommend");
     ctx->watch.recommend(ctx, ctx->d_uptr.as<uint32_t>(), ctx->d_upart.as<uint32_t>(), topn, flags, risk, items, mean,
@@ -172,7 +233,7 @@ int sbmf_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double risk, ui
 int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
-    list_scope(ctx, ctx->watch, "sbmf_watch_timing", false);
+    list_scope(ctx, ctx->watch.what, "sbmf_watch_timing", false);
     list_registered(ctx->watch, "sbmf_watch_timing");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     if (ms_score) {
@@ -182,15 +243,16 @@ int sbmf_watch_timing(sbmf_ctx* ctx, double* ms_score, double* ms_select) {
             *ms_score = sbmf::ev_ms(ctx->wev[0], ctx->wev[1]);
         }
     }
-    if (ms_select) *ms_select = ctx->watch.timed_select ? sbmf::ev_ms(ctx->watch.sel[0], ctx->watch.sel[1]) : 0.0;
+    if (ms_select) *ms_select = ctx->watch.sel.ms();
     API_END(ctx)
 }
 
 // --- fold-in list ----------------------------------------------------------------------------
 static void foldin_drop(sbmf_ctx* c) {
     c->guests.drop();
-    for (sbmf::DBuf* d : {&c->d_fptr, &c->d_fitems, &c->d_fratings, &c->d_forder, &c->d_fG, &c->d_fE, &c->d_fhyp})
-        d->release();
+    c->fcsr.drop();
+    c->d_fG.release();
+    c->d_fhyp.release();
     sbmf::pinned_free(c->h_fhyp, c->h_fhyp_bytes);
     c->h_fhyp_bytes = 0;
     for (hipEvent_t& e : c->fev) sbmf::event_destroy(e);
@@ -206,19 +268,10 @@ int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint
                       uint32_t flags) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
-    list_scope(ctx, ctx->guests, "sbmf_foldin_users", true);
+    list_scope(ctx, ctx->guests.what, "sbmf_foldin_users", true);
     if (flags & ~1u) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: unknown flags 0x%x (bit 0 = clamp)", flags & ~1u);
-    if (n && !ptr) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null ptr with n > 0");
-    if (n >= 0xfffffffeu) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: %u guests are too many", n);
-    for (uint32_t g = 0; g < n; ++g)
-        if (ptr[g + 1] < ptr[g])
-            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: ptr decreases at guest %u (%u then %u)", g, ptr[g], ptr[g + 1]);
-    const uint32_t p0 = n ? ptr[0] : 0, nnz = n ? ptr[n] - p0 : 0;
-    if (nnz && (!items || !ratings)) sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: null items / ratings with ratings listed");
-    for (uint32_t q = 0; q < nnz; ++q)
-        if (items[p0 + q] >= ctx->J)
-            sbmf::fail(SBMF_E_ARG, "sbmf_foldin_users: items[%u] = %u is not below the %u items", p0 + q, items[p0 + q],
-                       ctx->J);
+    sbmf::GuestCSR::check("sbmf_foldin_users", n, ptr, items, ratings, ctx->J);
+    const uint32_t nnz = n ? ptr[n] - ptr[0] : 0;
     list_sync(ctx);
     foldin_drop(ctx);
     if (n == 0) return SBMF_OK;
@@ -228,34 +281,16 @@ int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint
     const size_t b_tot = 2 * b_sum + b_G + ((size_t)n + 1 + 2 * (size_t)n + nnz) * sizeof(uint32_t) +
                          ((size_t)2 * nnz + 2 * Kp) * sizeof(double);
     try {
-        std::vector<uint32_t> hp(n + 1), ident(n);
-        for (uint32_t g = 0; g <= n; ++g) hp[g] = ptr[g] - p0;  // the device CSR starts at 0
-        for (uint32_t g = 0; g < n; ++g) ident[g] = g;
-        // the launch ends with its longest row: those start first
-        std::vector<uint32_t> order(ident);
-        std::stable_sort(order.begin(), order.end(),
-                         [&](uint32_t a, uint32_t b) { return hp[a + 1] - hp[a] > hp[b + 1] - hp[b]; });
         hipStream_t st = ctx->st;
         ctx->guests.alloc(n, ctx->J, (int)(flags & 1u), st);
         ctx->d_fG.alloc(b_G);
-        ctx->d_fE.alloc((size_t)nnz * sizeof(double));
         ctx->d_fhyp.alloc((size_t)2 * Kp * sizeof(double));
-        ctx->d_fptr.alloc(hp.size() * sizeof(uint32_t));
-        ctx->d_forder.alloc(order.size() * sizeof(uint32_t));
-        ctx->d_fitems.alloc((size_t)nnz * sizeof(uint32_t));
-        ctx->d_fratings.alloc((size_t)nnz * sizeof(double));
         sbmf::pinned_alloc((void**)&ctx->h_fhyp, (size_t)2 * Kp * sizeof(double));
         ctx->h_fhyp_bytes = (size_t)2 * Kp * sizeof(double);
         for (hipEvent_t& e : ctx->fev) sbmf::event_create(&e);
         HIPCHK(hipMemsetAsync(ctx->d_fG.p, 0, b_G, st));
-        HIPCHK(hipMemcpyAsync(ctx->d_fptr.p, hp.data(), hp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->guests.d_ids.p, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->d_forder.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (nnz) {
-            HIPCHK(hipMemcpyAsync(ctx->d_fitems.p, items + p0, (size_t)nnz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(ctx->d_fratings.p, ratings + p0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
+        // one slice: the whole list in one launch (the upload's synchronisation covers the memsets)
+        ctx->fcsr.upload(n, ptr, items, ratings, n, st, ctx->guests.d_ids.as<uint32_t>());
     } catch (const sbmf::Error& e) {
         foldin_drop(ctx);
         if (e.code == SBMF_E_NOMEM)
@@ -272,7 +307,7 @@ int sbmf_foldin_users(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint
 int sbmf_foldin_factors(sbmf_ctx* ctx, double* rows) {
     API_BEGIN
     if (!ctx || !rows) sbmf::fail(SBMF_E_ARG, "null argument");
-    list_scope(ctx, ctx->guests, "sbmf_foldin_factors", true);
+    list_scope(ctx, ctx->guests.what, "sbmf_foldin_factors", true);
     foldin_ready(ctx, "sbmf_foldin_factors", false);
     sbmf::download_table(ctx, ctx->d_fG, rows, ctx->guests.n);
     API_END(ctx)
@@ -281,7 +316,7 @@ int sbmf_foldin_factors(sbmf_ctx* ctx, double* rows) {
 int sbmf_foldin_scores(sbmf_ctx* ctx, uint32_t g, double* mean, double* stdev) {
     API_BEGIN
     if (!ctx || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
-    list_scope(ctx, ctx->guests, "sbmf_foldin_scores", true);
+    list_scope(ctx, ctx->guests.what, "sbmf_foldin_scores", true);
     foldin_ready(ctx, "sbmf_foldin_scores", true);
     ctx->guests.scores(ctx, "sbmf_foldin_scores", g, mean, stdev);
     API_END(ctx)
@@ -291,11 +326,11 @@ int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double r
                           double* stdev) {
     API_BEGIN
     if (!ctx || !items || !mean) sbmf::fail(SBMF_E_ARG, "null argument");
-    list_scope(ctx, ctx->guests, "sbmf_foldin_recommend", true);
+    list_scope(ctx, ctx->guests.what, "sbmf_foldin_recommend", true);
     recommend_args("sbmf_foldin_recommend", topn, flags, risk);
     foldin_ready(ctx, "sbmf_foldin_recommend", true);
     // "rated": the guest's own items (the guest CSR in the user-side CSR's place)
-    ctx->guests.recommend(ctx, ctx->d_fptr.as<uint32_t>(), ctx->d_fitems.as<uint32_t>(), topn, flags, risk, items, mean,
+    ctx->guests.recommend(ctx, ctx->fcsr.d_ptr.as<uint32_t>(), ctx->fcsr.d_items.as<uint32_t>(), topn, flags, risk, items, mean,
                           stdev);
     API_END(ctx)
 }
@@ -303,7 +338,7 @@ int sbmf_foldin_recommend(sbmf_ctx* ctx, uint32_t topn, uint32_t flags, double r
 int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double* ms_select) {
     API_BEGIN
     if (!ctx) sbmf::fail(SBMF_E_ARG, "null context");
-    list_scope(ctx, ctx->guests, "sbmf_foldin_timing", true);
+    list_scope(ctx, ctx->guests.what, "sbmf_foldin_timing", true);
     list_registered(ctx->guests, "sbmf_foldin_timing");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     if (ms_draw) *ms_draw = 0.0;
@@ -315,7 +350,7 @@ int sbmf_foldin_timing(sbmf_ctx* ctx, double* ms_draw, double* ms_score, double*
         // sweep's draw end is its begin)
         if (ms_score && ctx->guests.count) *ms_score = sbmf::ev_ms(ctx->fev[1], ctx->fev[2]);
     }
-    if (ms_select) *ms_select = ctx->guests.timed_select ? sbmf::ev_ms(ctx->guests.sel[0], ctx->guests.sel[1]) : 0.0;
+    if (ms_select) *ms_select = ctx->guests.sel.ms();
     API_END(ctx)
 }
 
@@ -327,14 +362,12 @@ static void fmq_drop(sbmf_ctx* c) {
 }
 // The contexts the query list covers: the general libFM learner with relations, on one rank.
 static void fmq_scope(const sbmf_ctx* c, const char* fn) {
-    if (c->virt) sbmf::fail(SBMF_E_STATE, "%s: a virtual rank's numbers are not a chain; no query list there", fn);
-    if (c->nranks > 1 || c->comm->active() || c->comm != &c->own_comm)
-        sbmf::fail(SBMF_E_STATE, "%s: the query list runs on one rank; this context joined a communicator", fn);
+    sbmf::one_real_rank(c, "query list", fn);
     if (c->cfg.method != SBMF_METHOD_LIBFM_MCMC && c->cfg.method != SBMF_METHOD_ALS)
         sbmf::fail(SBMF_E_STATE, "%s: the query list is offered by libFM's MCMC / ALS learner (SBMF_METHOD_LIBFM_MCMC, "
                                  "SBMF_METHOD_ALS) only; this context runs the %s (its lists: sbmf_watch_users, "
                                  "sbmf_foldin_users)", fn, c->cfg.method == SBMF_METHOD_VB ? "online VB learner" : "SBPMF sampler");
-    if (!c->prepared) sbmf::fail(SBMF_E_STATE, "%s: not prepared (sbmf_prepare)", fn);
+    sbmf::is_prepared(c, fn);
     if (!c->fm || c->fm->rel_info.empty())
         sbmf::fail(SBMF_E_STATE, "%s: this context has no relations (sbmf_add_relation): the candidates of a query "
                                  "list are the block rows of one", fn);
@@ -503,7 +536,7 @@ int sbmf_fm_query_timing(sbmf_ctx* ctx, double* ms_terms, double* ms_score, doub
         if (ms_terms) *ms_terms = sbmf::ev_ms(ctx->fmqd.ev[0], ctx->fmqd.ev[1]);
         if (ms_score) *ms_score = sbmf::ev_ms(ctx->fmqd.ev[1], ctx->fmqd.ev[2]);
     }
-    if (ms_select) *ms_select = ctx->fmq.timed_select ? sbmf::ev_ms(ctx->fmq.sel[0], ctx->fmq.sel[1]) : 0.0;
+    if (ms_select) *ms_select = ctx->fmq.sel.ms();
     API_END(ctx)
 }
 

@@ -759,10 +759,10 @@ struct SweepRun {
             std::copy(hy.mu_u.begin(), hy.mu_u.begin() + K, h + Kp);
             HIPCHK(hipMemcpyAsync(c->d_fhyp.p, h, 2 * Kp * sizeof(double), hipMemcpyHostToDevice, se));
             HIPCHK(hipEventRecord(c->fev[0], se));
-            HIPCHK(launch_foldin<T>(c->guests.n, c->d_forder.as<uint32_t>(), c->d_fptr.as<uint32_t>(),
-                                    c->d_fitems.as<uint32_t>(), c->d_fratings.as<double>(), c->d_fG.as<T>(),
+            HIPCHK(launch_foldin<T>(c->guests.n, c->fcsr.d_order.as<uint32_t>(), c->fcsr.d_ptr.as<uint32_t>(),
+                                    c->fcsr.d_items.as<uint32_t>(), c->fcsr.d_ratings.as<double>(), c->d_fG.as<T>(),
                                     c->d_V.as<T>(), K, c->Kp, c->d_fhyp.as<double>(), hy.tau, c->sd_is_var, cf.seed,
-                                    c->sweep, c->d_fE.as<double>(), se));
+                                    c->sweep, c->fcsr.d_E.as<double>(), se));
             HIPCHK(hipEventRecord(c->fev[1], se));
             c->fdrawn++;
             c->launches++;

@@ -448,6 +448,32 @@ class FMLearnSBPMF:
         if rc != SBMF_OK:
             raise SBMFError(rc, lib.sbmf_last_error(self.ctx).decode())
 
+    # what the score lists' and the sample store's wrappers share: ``fn`` is the library's entry
+    # point, ``args`` its arguments between the context and the outputs
+    def _topn(self, fn, n, topn, *args):
+        """A top-N call for ``n`` rows: (ids int64 [n, topn] with -1 in empty slots, mean, stdev)."""
+        if not 0 <= int(topn) <= 0xffffffff:
+            raise ValueError("topn must be a non-negative 32-bit count")
+        t = int(topn)
+        ids = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
+        mean, sd = np.full(ids.shape, np.nan), np.full(ids.shape, np.nan)
+        self._check(fn(self.ctx, *args, _ptr(ids, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        out = ids[:n, :t].astype(np.int64)
+        out[out == 0xffffffff] = -1
+        return out, mean[:n, :t], sd[:n, :t]
+
+    def _scores(self, fn, width, *args):
+        """A (mean, stdev) call with ``width`` values each."""
+        mean, sd = np.zeros(max(width, 1)), np.zeros(max(width, 1))
+        self._check(fn(self.ctx, *args, _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
+        return mean[:width], sd[:width]
+
+    def _ms(self, fn, *names):
+        """A timing call: {name: device ms}."""
+        ms = [C.c_double() for _ in names]
+        self._check(fn(self.ctx, *[C.byref(m) for m in ms]))
+        return {k: m.value for k, m in zip(names, ms)}
+
     def set_groups(self, group):
         """libFM's -meta: group[a] is the attribute group of attribute a, for every a < num_attribute
         (the largest attribute id over train and test + 2; for triples user u is attribute u and
@@ -646,32 +672,19 @@ class FMLearnSBPMF:
     def watch_scores(self, w):
         """(mean, stdev) of watched user ``w`` (index into the list) over the sweeps
         collected since ``watch``, one value per item."""
-        _, ni, _, _ = self.dims()
-        mean, sd = np.zeros(ni), np.zeros(ni)
-        self._check(lib.sbmf_watch_scores(self.ctx, int(w), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        return mean, sd
+        return self._scores(lib.sbmf_watch_scores, self.dims()[1], int(w))
 
     def recommend(self, topn=10, exclude_rated=True, risk=0.0):
         """Per watched user the ``topn`` items with the largest mean - risk * stdev (ties by
         ascending item id), without the items the user rated in training unless
         ``exclude_rated`` is False.  Returns (items int64 [n, topn] with -1 in empty
         slots, mean, stdev); empty slots hold NaN."""
-        if not 0 <= int(topn) <= 0xffffffff:
-            raise ValueError("topn must be a non-negative 32-bit count")
-        n, t = getattr(self, "_n_watch", 0), int(topn)
-        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
-        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
-        self._check(lib.sbmf_recommend(self.ctx, t, 0 if exclude_rated else 1, float(risk), _ptr(items, C.c_uint32),
-                                       _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        out = items[:n, :t].astype(np.int64)
-        out[out == 0xffffffff] = -1
-        return out, mean[:n, :t], sd[:n, :t]
+        return self._topn(lib.sbmf_recommend, getattr(self, "_n_watch", 0), topn, int(topn), 0 if exclude_rated else 1,
+                          float(risk))
 
     def watch_timing(self):
         """Device ms of the last sweep's scoring launch and of the last selection."""
-        a, b = C.c_double(), C.c_double()
-        self._check(lib.sbmf_watch_timing(self.ctx, C.byref(a), C.byref(b)))
-        return {"ms_score": a.value, "ms_select": b.value}
+        return self._ms(lib.sbmf_watch_timing, "ms_score", "ms_select")
 
     # -- posterior sample store: thinned samples of the chain kept on the device, scored after the run
     def keep_samples(self, every=1, cap=64):
@@ -697,43 +710,27 @@ class FMLearnSBPMF:
 
     def samples_scores(self, user, clamp=False):
         """(mean, stdev) of ``user``'s score of every item over the stored samples."""
-        _, ni, _, _ = self.dims()
-        mean, sd = np.zeros(ni), np.zeros(ni)
-        self._check(lib.sbmf_samples_scores(self.ctx, int(user), 2 if clamp else 0, _ptr(mean, C.c_double),
-                                            _ptr(sd, C.c_double)))
-        return mean, sd
+        return self._scores(lib.sbmf_samples_scores, self.dims()[1], int(user), 2 if clamp else 0)
 
     def samples_recommend(self, users, topn=10, exclude_rated=True, risk=0.0, clamp=False):
         """``recommend`` for any users, named now, from the stored samples: (items int64
         [n, topn] with -1 in empty slots, mean, stdev)."""
         users = _u32(users).ravel()
-        if not 0 <= int(topn) <= 0xffffffff:
-            raise ValueError("topn must be a non-negative 32-bit count")
-        n, t = len(users), int(topn)
-        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
-        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
         flags = (0 if exclude_rated else 1) | (2 if clamp else 0)
-        self._check(lib.sbmf_samples_recommend(self.ctx, n, _ptr(users, C.c_uint32), t, flags, float(risk),
-                                               _ptr(items, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        out = items[:n, :t].astype(np.int64)
-        out[out == 0xffffffff] = -1
-        return out, mean[:n, :t], sd[:n, :t]
+        return self._topn(lib.sbmf_samples_recommend, len(users), topn, len(users), _ptr(users, C.c_uint32), int(topn),
+                          flags, float(risk))
 
     def samples_predict(self, users, items, clamp=False):
         """(mean, stdev) of the pairs (users[p], items[p]) over the stored samples."""
         users, items = _u32(users).ravel(), _u32(items).ravel()
         if len(users) != len(items):
             raise ValueError("users and items must have the same length")
-        mean, sd = np.zeros(len(users)), np.zeros(len(users))
-        self._check(lib.sbmf_samples_predict(self.ctx, len(users), _ptr(users, C.c_uint32), _ptr(items, C.c_uint32),
-                                             2 if clamp else 0, _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        return mean, sd
+        return self._scores(lib.sbmf_samples_predict, len(users), len(users), _ptr(users, C.c_uint32),
+                            _ptr(items, C.c_uint32), 2 if clamp else 0)
 
     def samples_timing(self):
         """Device ms of the last copy into the store, the last scoring launch and the last selection."""
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._check(lib.sbmf_samples_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
-        return {"ms_copy": a.value, "ms_score": b.value, "ms_select": c.value}
+        return self._ms(lib.sbmf_samples_timing, "ms_copy", "ms_score", "ms_select")
 
     def save_samples(self, path):
         self._check(lib.sbmf_save_samples(self.ctx, str(path).encode()))
@@ -765,18 +762,9 @@ class FMLearnSBPMF:
         takes): (items int64 [n, topn] with -1 in empty slots, mean, stdev).  ``scans``: coordinate
         scans per sample (sbmf_samples_foldin_recommend)."""
         n, ptr, items, ratings = _guest_csr(guests)
-        if not 0 <= int(topn) <= 0xffffffff:
-            raise ValueError("topn must be a non-negative 32-bit count")
-        t = int(topn)
-        out = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
-        mean, sd = np.full(out.shape, np.nan), np.full(out.shape, np.nan)
         flags = (0 if exclude_rated else 1) | (2 if clamp else 0)
-        self._check(lib.sbmf_samples_foldin_recommend(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
-                                                      _ptr(ratings, C.c_double), int(scans), t, flags, float(risk),
-                                                      _ptr(out, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        out = out[:n, :t].astype(np.int64)
-        out[out == 0xffffffff] = -1
-        return out, mean[:n, :t], sd[:n, :t]
+        return self._topn(lib.sbmf_samples_foldin_recommend, n, topn, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                          _ptr(ratings, C.c_double), int(scans), int(topn), flags, float(risk))
 
     def samples_foldin_rows(self, guests, scans=1):
         """The guests' factor rows at every stored sample, [count, n, K], oldest sample first."""
@@ -793,18 +781,12 @@ class FMLearnSBPMF:
         items, ratings = _u32(np.asarray(items, dtype=np.int64).ravel()), _f64(np.asarray(ratings, dtype=np.float64).ravel())
         if len(items) != len(ratings):
             raise ValueError("items and ratings differ in length")
-        _, ni, _, _ = self.dims()
-        mean, sd = np.zeros(ni), np.zeros(ni)
-        self._check(lib.sbmf_samples_foldin_scores(self.ctx, len(items), _ptr(items, C.c_uint32), _ptr(ratings, C.c_double),
-                                                   int(scans), 2 if clamp else 0, _ptr(mean, C.c_double),
-                                                   _ptr(sd, C.c_double)))
-        return mean, sd
+        return self._scores(lib.sbmf_samples_foldin_scores, self.dims()[1], len(items), _ptr(items, C.c_uint32),
+                            _ptr(ratings, C.c_double), int(scans), 2 if clamp else 0)
 
     def samples_foldin_timing(self):
         """Device ms of the last guest call's draw, scoring launch and selection (its last slice)."""
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._check(lib.sbmf_samples_foldin_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
-        return {"ms_draw": a.value, "ms_score": b.value, "ms_select": c.value}
+        return self._ms(lib.sbmf_samples_foldin_timing, "ms_draw", "ms_score", "ms_select")
 
     # -- posterior top-N for guests: users outside the training set, given by their ratings
     def foldin(self, guests, clamp=False):
@@ -826,29 +808,16 @@ class FMLearnSBPMF:
 
     def foldin_scores(self, g):
         """(mean, stdev) of guest ``g`` over the sweeps collected since ``foldin``, one value per item."""
-        _, ni, _, _ = self.dims()
-        mean, sd = np.zeros(ni), np.zeros(ni)
-        self._check(lib.sbmf_foldin_scores(self.ctx, int(g), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        return mean, sd
+        return self._scores(lib.sbmf_foldin_scores, self.dims()[1], int(g))
 
     def foldin_recommend(self, topn=10, exclude_rated=True, risk=0.0):
         """``recommend`` for the guests; "rated" means the guest's own items."""
-        if not 0 <= int(topn) <= 0xffffffff:
-            raise ValueError("topn must be a non-negative 32-bit count")
-        n, t = getattr(self, "_n_guests", 0), int(topn)
-        items = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
-        mean, sd = np.full(items.shape, np.nan), np.full(items.shape, np.nan)
-        self._check(lib.sbmf_foldin_recommend(self.ctx, t, 0 if exclude_rated else 1, float(risk),
-                                              _ptr(items, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        out = items[:n, :t].astype(np.int64)
-        out[out == 0xffffffff] = -1
-        return out, mean[:n, :t], sd[:n, :t]
+        return self._topn(lib.sbmf_foldin_recommend, getattr(self, "_n_guests", 0), topn, int(topn),
+                          0 if exclude_rated else 1, float(risk))
 
     def foldin_timing(self):
         """Device ms of the last sweep's draw and scoring launch and of the last selection."""
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._check(lib.sbmf_foldin_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
-        return {"ms_draw": a.value, "ms_score": b.value, "ms_select": c.value}
+        return self._ms(lib.sbmf_foldin_timing, "ms_draw", "ms_score", "ms_select")
 
     # -- posterior top-N of query cases over a relation's block rows (libFM's MCMC / ALS learner)
     def fm_queries(self, relation, cases, rows=None, exclude=None, clamp=False):
@@ -895,32 +864,19 @@ class FMLearnSBPMF:
     def fm_query_scores(self, q):
         """(mean, stdev) of query ``q`` over the iterations accumulated since ``fm_queries`` (ALS: the
         latest iteration, stdev 0), one value per block row of the candidates' relation."""
-        nb = getattr(self, "_query_rows", 0)
-        mean, sd = np.zeros(max(nb, 1)), np.zeros(max(nb, 1))
-        self._check(lib.sbmf_fm_query_scores(self.ctx, int(q), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        return mean[:nb], sd[:nb]
+        return self._scores(lib.sbmf_fm_query_scores, getattr(self, "_query_rows", 0), int(q))
 
     def fm_query_recommend(self, topn=10, risk=0.0, keep_excluded=False):
         """Per query the ``topn`` block rows with the largest mean - risk * stdev (ties by ascending
         row), without the query's excluded rows unless ``keep_excluded``.  Returns (rows int64
         [n, topn] with -1 in empty slots, mean, stdev); empty slots hold NaN."""
-        if not 0 <= int(topn) <= 0xffffffff:
-            raise ValueError("topn must be a non-negative 32-bit count")
-        n, t = getattr(self, "_n_queries", 0), int(topn)
-        rows = np.full((max(n, 1), max(t, 1)), 0xffffffff, dtype=np.uint32)
-        mean, sd = np.full(rows.shape, np.nan), np.full(rows.shape, np.nan)
-        self._check(lib.sbmf_fm_query_recommend(self.ctx, t, 1 if keep_excluded else 0, float(risk),
-                                                _ptr(rows, C.c_uint32), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
-        out = rows[:n, :t].astype(np.int64)
-        out[out == 0xffffffff] = -1
-        return out, mean[:n, :t], sd[:n, :t]
+        return self._topn(lib.sbmf_fm_query_recommend, getattr(self, "_n_queries", 0), topn, int(topn),
+                          1 if keep_excluded else 0, float(risk))
 
     def fm_query_timing(self):
         """Device ms of the last iteration's query terms and operand copy, of its scoring launch,
         and of the last selection."""
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._check(lib.sbmf_fm_query_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
-        return {"ms_terms": a.value, "ms_score": b.value, "ms_select": c.value}
+        return self._ms(lib.sbmf_fm_query_timing, "ms_terms", "ms_score", "ms_select")
 
     def close(self):
         if self.ctx is not None:

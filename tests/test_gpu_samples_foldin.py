@@ -324,6 +324,62 @@ def test_slices_equal_the_unsliced_call(ml100k):
     L.close()
 
 
+def test_null_stdev_on_a_partial_last_slice(stored, ml100k):
+    """Slices of 64, 64 and 22 rows with stdev = NULL: items and mean are those of the call that
+    takes a stdev, for users and for guests (the one selection helper's offsets on the last slice)."""
+    L, _ = stored
+    tr, _ = ml100k
+    rng = np.random.default_rng(12)
+    users = rng.permutation(943)[:150].astype(np.uint32)
+    n, ptr, gi, gr = sbmf._guest_csr([(rng.permutation(J)[:k].astype(np.uint32), rng.choice(tr[2], k))
+                                      for k in rng.integers(0, 40, 150)])
+    u32, f64 = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    p = lambda a: a.ctypes.data_as(u32 if a.dtype == np.uint32 else f64)
+    # 64 rows: two sums of [64][Jp = 1696] doubles and four samples' rows of Kp = 32 doubles
+    assert lib.sbmf_test_samples_tune(L.ctx, 64 * (2 * 1696 * 8 + 4 * 32 * 8), 0) == 0
+
+    def call(who, with_sd):
+        items, mean, sd = np.full((150, 3), 0xfffffffe, np.uint32), np.full((150, 3), -7e7), np.full((150, 3), -7e7)
+        out = (p(items), p(mean), p(sd) if with_sd else None)
+        rc = (lib.sbmf_samples_recommend(L.ctx, 150, p(users), 3, 0, 0.5, *out) if who == "users" else
+              lib.sbmf_samples_foldin_recommend(L.ctx, n, p(ptr), p(gi), p(gr), 1, 3, 0, 0.5, *out))
+        assert rc == 0, lib.sbmf_last_error(L.ctx)
+        return items, mean, sd
+
+    try:
+        for who in ("users", "guests"):
+            items, mean, sd = call(who, True)
+            assert not np.any(items == 0xfffffffe) and not np.any(mean == -7e7) and not np.any(sd == -7e7)  # every slot written
+            i0, m0, s0 = call(who, False)
+            assert np.array_equal(i0, items) and np.array_equal(m0, mean, equal_nan=True), who
+            assert np.all(s0 == -7e7)  # nothing written where no stdev was asked for
+    finally:
+        assert lib.sbmf_test_samples_tune(L.ctx, 0, 0) == 0
+
+
+def test_guest_csr_that_does_not_start_at_zero(stored, ml100k):
+    """ptr[0] = 5 with five junk entries in front, an empty guest and one that holds all the rest:
+    the in-chain list and the stored samples' guests are the rebased CSR's, bit for bit."""
+    L, _ = stored
+    tr, _ = ml100k
+    rng = np.random.default_rng(13)
+    items = rng.permutation(J)[:43].astype(np.uint32)
+    ratings = rng.choice(tr[2], 43)
+    based = (np.array([0, 3, 3, 43], np.uint32), items, ratings)
+    offset = (based[0] + 5, np.concatenate([np.full(5, 0xffffffff, np.uint32), items]),
+              np.concatenate([np.full(5, np.nan), ratings]))
+    assert np.array_equal(L.samples_foldin_rows(offset), L.samples_foldin_rows(based))
+    assert same(L.samples_foldin_recommend(offset, topn=5), L.samples_foldin_recommend(based, topn=5))
+    out = []
+    for csr in (based, offset):
+        C2 = learner(ml100k, rng="philox")
+        C2.foldin(csr)
+        C2.learn(sweeps=2)
+        out.append([C2.foldin_factors(), *C2.foldin_recommend(topn=5), *C2.foldin_scores(2)])
+        C2.close()
+    assert same(*out) and np.all(np.isfinite(out[0][0]))
+
+
 # ---- 6. nothing else moves
 def test_nothing_else_moves(ml100k):
     tr, _ = ml100k

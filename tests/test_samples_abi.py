@@ -150,6 +150,24 @@ def test_file_info_names_each_error(tmp_path):
     assert ei.value.code == sbmf.SBMF_E_IO and "cannot open" in str(ei.value)
 
 
+def test_file_info_whole_messages(tmp_path):
+    """Every refusal of the header reader, the whole text (the companion file's: test_samples_foldin_abi.py)."""
+    p, good = tmp_path / "s.bin", sample_file()
+    n = len(good)
+    cases = [(good[:39], "is truncated in its header: 39 bytes, a sample file's header has 40"),
+             (sample_file(magic=b"SBMFSHP\n"), "is not a sample file (bad magic)"),
+             (sample_file(version=2), "has the unknown format version 2; this build reads version 1"),
+             (sample_file(precision=2, body=b""), "has a bad header (precision 2, bias 0, K 4, count 2)"),
+             (sample_file(bias=2, K=257, count=65536, body=b""), "has a bad header (precision 0, bias 2, K 257, count 65536)"),
+             (good[:-1], "is truncated in its body: %d bytes, its header implies %d" % (n - 1, n)),
+             (good + b"\0\0\0", "has 3 trailing bytes: %d bytes, its header implies %d" % (n + 3, n))]
+    for data, text in cases:
+        assert info_error(tmp_path, data) == "sbmf error -4: sbmf_samples_file_info: %s %s" % (p, text)
+    with pytest.raises(sbmf.SBMFError) as ei:
+        sbmf.samples_file_info(tmp_path / "missing")
+    assert str(ei.value) == "sbmf error -4: sbmf_samples_file_info: cannot open %s" % (tmp_path / "missing")
+
+
 # ---- the command line: decided by the flags alone, nothing opened
 BASE = ("-task", "r", "-train", "/nonexistent/train", "-test", "/nonexistent/test")
 REFUSAL = "ERROR: -samples_out / -samples_in are offered by the SBPMF sampler (-method mcmc -order sbpmf)"

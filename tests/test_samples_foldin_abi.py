@@ -135,6 +135,23 @@ def test_file_info_names_each_error(tmp_path):
     assert ei.value.code == sbmf.SBMF_E_IO and "cannot open" in str(ei.value)
 
 
+def test_file_info_whole_messages(tmp_path):
+    """Every refusal of the header reader, the whole text (the sample file's: test_samples_abi.py)."""
+    p, good = tmp_path / "h.bin", hyper_file()
+    n = len(good)
+    cases = [(good[:23], "is truncated in its header: 23 bytes, a sample hyperparameter file's header has 24"),
+             (hyper_file(magic=b"SBMFSMP\n"), "is not a sample hyperparameter file (bad magic)"),
+             (hyper_file(version=2), "has the unknown format version 2; this build reads version 1"),
+             (hyper_file(K=257, count=65536, reserved=1), "has a bad header (K 257, count 65536, reserved 1)"),
+             (good[:-1], "is truncated in its body: %d bytes, its header implies %d" % (n - 1, n)),
+             (good + b"\0\0\0", "has 3 trailing bytes: %d bytes, its header implies %d" % (n + 3, n))]
+    for data, text in cases:
+        assert info_error(tmp_path, data) == "sbmf error -4: sbmf_samples_hyper_file_info: %s %s" % (p, text)
+    with pytest.raises(sbmf.SBMFError) as ei:
+        sbmf.samples_hyper_file_info(tmp_path / "missing")
+    assert str(ei.value) == "sbmf error -4: sbmf_samples_hyper_file_info: cannot open %s" % (tmp_path / "missing")
+
+
 # ---- the command line: decided by the flags alone, nothing opened
 BASE = ("-task", "r", "-train", "/nonexistent/train", "-test", "/nonexistent/test")
 SERVE = ("-samples_in", "f", "-samples_hyper_in", "h", "-samples_recommend_guests", "o", "-samples_guests", "g")
