@@ -26,7 +26,8 @@ Fixtures written (all data, no reference source):
                                               libFM's stdout "#Iter=..." lines of bin/libFM -method
                                               mcmc|als (libfm.cpp compiled unmodified, time() pinned
                                               to <seed> by oracle/ref_pin_time.c) on the users-first
-                                              libFM text of the data set
+                                              libFM text of the data set; data edge: the set
+                                              tests/fm_edge.py takes from tests/edge_rows.py
   ref_libfm_<...>_pred.txt.gz                 its -out file (averaged clamped test predictions)
   ref_final_ml1msynth_k20_s1.txt              gibbs_sbpmf_final on the ML-1M-shaped synthetic set
                                               (sbmf/synth.py), through its long-chain collapse
@@ -187,7 +188,8 @@ def vbo_goldens():
 # (method, data, dim, seed = pinned time(), iterations, -regular)
 LIBFM_RUNS = [("mcmc", "ml100k", "1,1,8", 1, 10, None), ("als", "ml100k", "1,1,8", 1, 10, "0,0,10"),
               ("mcmc", "ml100k", "0,0,20", 7, 20, None), ("mcmc", "ragged", "1,1,8", 3, 20, None),
-              ("als", "ragged", "1,1,4", 2, 10, "1,2,5")]
+              ("als", "ragged", "1,1,4", 2, 10, "1,2,5"), ("mcmc", "edge", "1,1,8", 2, 3, None),
+              ("als", "edge", "1,1,8", 2, 3, "0.5,1,4")]
 
 
 def libfm_name(method, dname, dim, seed, iters):
@@ -200,10 +202,17 @@ def libfm_goldens():
     sets = {"ml100k": (os.path.join(GOLD, "ml100k_train.tsv.gz"), os.path.join(GOLD, "ml100k_test.tsv.gz")),
             "ragged": (os.path.join(GOLD, "ragged_train.tsv"), os.path.join(GOLD, "ragged_test.tsv"))}
     for method, dname, dim, seed, iters, reg in LIBFM_RUNS:
-        tr, te = sets[dname]
-        I = max_user(tr, te) + 1
-        write_libfm(tr, os.path.join(root, "train.libfm"), I)
-        write_libfm(te, os.path.join(root, "test.libfm"), I)
+        if dname == "edge":  # the row-form edge set: tests/edge_rows.py is the data, no file is stored
+            sys.path.insert(0, os.path.join(REPO, "tests"))
+            import fm_edge
+            etr, ete, (I, _) = fm_edge.generate()
+            write_libfm_arrays(os.path.join(root, "train.libfm"), etr, I)
+            write_libfm_arrays(os.path.join(root, "test.libfm"), ete, I)
+        else:
+            tr, te = sets[dname]
+            I = max_user(tr, te) + 1
+            write_libfm(tr, os.path.join(root, "train.libfm"), I)
+            write_libfm(te, os.path.join(root, "test.libfm"), I)
         cmd = [os.path.join(HERE, "_ref", "libFM"), "-task", "r", "-train", "train.libfm", "-test", "test.libfm",
                "-dim", dim, "-iter", str(iters), "-method", method, "-out", "pred.txt"]
         if reg:

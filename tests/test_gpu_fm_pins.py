@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import fm_cases
+import fm_edge
 import fm_groups
 from conftest import GOLD, gpu_available
 from sbmf import Data, FMLearnSBPMF, SBMFError
@@ -92,14 +93,14 @@ def _learner(method="mcmc", rng="ref", dim=(1, 1, 4), regular=(0.0, 0.0, 0.0), s
                         regular=regular, init_stdev=0.1)
 
 
-def _run(train, test, general, iters=3, stop_then_one=False, group=None, **kw):
+def _run(train, test, general, iters=3, stop_then_one=False, group=None, dims=(0, 0), **kw):
     """The pins of one run: `iters` iterations, or (stop_then_one) five iterations whose callback
     stops after the second, then one more learn(1) -- the break and the carried iteration count."""
     L = _learner(**kw)
     if group is not None:
         L.set_groups(group)
     try:
-        L.set_data(train, test)
+        L.set_data(train, test, num_users=dims[0], num_items=dims[1])
     except SBMFError as e:
         L.close()
         return {"error_code": int(e.code), "error": str(e)}
@@ -156,6 +157,35 @@ def test_two_attribute_two_ranks(method, regular, tmp_path):
     rec = {k: _digest(z0[k]) for k in keys}
     rec["n_launch"] = int(z0["n_launch"][0])
     _check("two/ragged/2ranks-" + method, rec)
+
+
+# the row-form edge set of tests/fm_edge.py at tests/test_gpu_fm_edge.py's settings: rows of 0 .. 4097
+# cases on both sides, the 4097-case rows in two chunks or (chunk0) whole with a tail case
+TWO_EDGE = {"mcmc-ref": {}, "mcmc-philox": dict(rng="philox"), "als": dict(method="als", regular=(0.5, 1.0, 4.0)),
+            "chunk0-mcmc-ref": dict(env={"SBMF_FMM_CHUNK": "0"})}
+
+
+@pytest.mark.parametrize("case", sorted(TWO_EDGE))
+def test_two_attribute_edge_set(case, monkeypatch):
+    assert gpu_available()
+    kw = dict(TWO_EDGE[case])
+    for k, v in kw.pop("env", {}).items():
+        monkeypatch.setenv(k, v)
+    tr, te, dims = fm_edge.generate()
+    _check("two/edge/" + case, _run(Data(*tr), Data(*te), False, dims=dims, dim=(1, 1, 8), seed=2, **kw))
+
+
+def test_two_attribute_edge_set_two_ranks(tmp_path):
+    """The user rows of 4097 cases whole on their rank, the item rows by their share on each."""
+    assert gpu_available()
+    outs = _run_ranks(tmp_path, 2, ["8", "3", "2", "ref", "0", "1,1;0,0,0", "libfm"], env={"SBMF_WORKER_DATA": "edge"})
+    z0, z1 = np.load(outs[0]), np.load(outs[1])
+    keys = ("rmse_train", "rmse", "rmse_this", "tau", "pred", "U", "V", "bu", "bv", "b0", "hyper")
+    for k in keys:
+        assert np.array_equal(z1[k], z0[k], equal_nan=True), k
+    rec = {k: _digest(z0[k]) for k in keys}
+    rec["n_launch"] = int(z0["n_launch"][0])
+    _check("two/edge/2ranks-mcmc", rec)
 
 
 # ---- the general learner

@@ -12,15 +12,15 @@ import pytest
 import oracle
 from conftest import GOLD, gpu_available
 from sbmf import Data, FMLearnSBPMF
-from test_oracle_libfm import RUNS, golden_name
+from test_oracle_libfm import RUNS, golden_name, run_data
 
 pytestmark = pytest.mark.gpu
 
 
-def _gpu(tr, te, K, iters, seed, method, k0, k1, regular, rng="ref"):
+def _gpu(tr, te, K, iters, seed, method, k0, k1, regular, rng="ref", dims=(0, 0)):
     L = FMLearnSBPMF(num_factor=K, seed=seed, rng=rng, method="als" if method == "als" else "mcmc", order="libfm",
                      k0=k0, k1=k1, regular=regular, init_stdev=0.1)
-    L.set_data(Data(*tr), Data(*te))
+    L.set_data(Data(*tr), Data(*te), num_users=dims[0], num_items=dims[1])
     L.learn(sweeps=iters)
     return L
 
@@ -36,11 +36,12 @@ def _within_printed(x, printed):
 def test_libfm_chain_matches_reference(run, ml100k, ragged):
     assert gpu_available()
     method, dname, dim, seed, iters, reg = run
-    tr, te = ml100k if dname == "ml100k" else ragged
+    tr, te, dims = run_data(dname, ml100k, ragged)
     k0, k1, K = (int(x) for x in dim.split(","))
     regular = tuple(float(x) for x in reg.split(",")) if reg else (0.0, 0.0, 0.0)
-    L = _gpu(tr, te, K, iters, seed, method, k0, k1, regular)
-    o = oracle.run_fmm(tr, te, K=K, iters=iters, seed=seed, method=method, k0=k0, k1=k1, regular=regular)
+    L = _gpu(tr, te, K, iters, seed, method, k0, k1, regular, dims=dims)
+    o = oracle.run_fmm(tr, te, K=K, iters=iters, seed=seed, method=method, k0=k0, k1=k1, regular=regular,
+                       num_users=dims[0])
     h = L.history
     train = np.array([x["rmse_train"] for x in h])
     test = np.array([x["rmse_avg"] for x in h])

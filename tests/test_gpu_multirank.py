@@ -159,9 +159,9 @@ def test_libfm_ranks_on_one_gpu(ml100k, ragged, tmp_path, nranks, run):
     users' w and v broadcast after each sweep): identical on every rank, one
     rank's run to rounding, and bin/libFM's printed digits (tests/golden)."""
     from test_gpu_libfm import _within_printed
-    from test_oracle_libfm import RUNS, golden_name
+    from test_oracle_libfm import RUNS, golden_name, run_data
     method, dname, dim, seed, iters, reg = RUNS[run]
-    tr, te = ml100k if dname == "ml100k" else ragged
+    tr, te, dims = run_data(dname, ml100k, ragged)
     k0, k1, K = (int(x) for x in dim.split(","))
     regular = reg or "0,0,0"
     L = FMLearnSBPMF(num_factor=K, seed=seed, order="libfm", method="als" if method == "als" else "mcmc", k0=k0,

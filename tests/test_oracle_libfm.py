@@ -16,7 +16,17 @@ from conftest import GOLD, read_libfm_text
 # (method, data, dim, seed, iterations, -regular) -- as oracle/make_golden.py LIBFM_RUNS
 RUNS = [("mcmc", "ml100k", "1,1,8", 1, 10, None), ("als", "ml100k", "1,1,8", 1, 10, "0,0,10"),
         ("mcmc", "ml100k", "0,0,20", 7, 20, None), ("mcmc", "ragged", "1,1,8", 3, 20, None),
-        ("als", "ragged", "1,1,4", 2, 10, "1,2,5")]
+        ("als", "ragged", "1,1,4", 2, 10, "1,2,5"), ("mcmc", "edge", "1,1,8", 2, 3, None),
+        ("als", "edge", "1,1,8", 2, 3, "0.5,1,4")]
+
+
+def run_data(dname, ml100k, ragged):
+    """(train, test, (num_users, num_items)) of a run's data set; "edge": the row-form edge set
+    of tests/fm_edge.py, whose empty last rows exist through its dims (else 0, 0: from the ids)."""
+    if dname == "edge":
+        import fm_edge
+        return fm_edge.generate()
+    return (ml100k if dname == "ml100k" else ragged) + ((0, 0),)
 
 
 def golden_name(method, dname, dim, seed, iters):
@@ -31,10 +41,11 @@ def iter_lines(res):
 @pytest.mark.parametrize("run", RUNS, ids=[golden_name(*r[:5]) for r in RUNS])
 def test_oracle_matches_compiled_libfm(run, ml100k, ragged):
     method, dname, dim, seed, iters, reg = run
-    tr, te = ml100k if dname == "ml100k" else ragged
+    tr, te, dims = run_data(dname, ml100k, ragged)
     k0, k1, K = (int(x) for x in dim.split(","))
     regular = tuple(float(x) for x in reg.split(",")) if reg else (0.0, 0.0, 0.0)
-    o = oracle.run_fmm(tr, te, K=K, iters=iters, seed=seed, method=method, k0=k0, k1=k1, regular=regular)
+    o = oracle.run_fmm(tr, te, K=K, iters=iters, seed=seed, method=method, k0=k0, k1=k1, regular=regular,
+                       num_users=dims[0])
     name = golden_name(method, dname, dim, seed, iters)
     with open(os.path.join(GOLD, name + ".txt")) as f:
         ref_lines = f.read().splitlines()

@@ -7,7 +7,8 @@ backend (the id was made with SBMF_COMM=host); the result must equal a
 single-rank run in the same residual form.  method "vb": the online VB
 learner (user ranges per rank, item sums all-gathered), `sweeps` epochs of
 `vb_batches` mini-batches (0: the reference's 30).  SBMF_WORKER_DATA=vbedge:
-the row-class edge set of tests/vb_edge.py.
+the row-class edge set of tests/vb_edge.py; SBMF_WORKER_DATA=edge: the row-form
+edge set of tests/fm_edge.py.
 """
 import gzip
 import os
@@ -52,6 +53,10 @@ def main():
         sys.path.insert(0, os.path.join(REPO, "tests"))
         import vb_edge
         tr, te, dims = vb_edge.generate()
+    elif data == "edge":
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import fm_edge
+        tr, te, dims = fm_edge.generate()
     else:
         tr, te = read(os.path.join(g, data + "_train.tsv.gz")), read(os.path.join(g, data + "_test.tsv.gz"))
     if method == "vb":
