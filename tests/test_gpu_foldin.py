@@ -28,6 +28,7 @@ import pytest
 
 from conftest import write_m1m100k_libfm
 from edge_rows import restate_row as restate  # the header's coordinate loop for one row in a floating type
+from sample_files import expected_topn  # the selection's order: one copy for the list tests
 from sbmf import (SBMF_E_ARG, SBMF_E_STATE, Data, FMLearnSBPMF, SBMFError, device_usage, philox_normals)
 from sbmf._lib import CLI_PATH, lib
 
@@ -188,19 +189,6 @@ class Moments:
         print("%s: n=%d  max|mean err| %.3e (bound %.3e)  max|2nd moment err| %.3e (bound %.3e)"
               % (what, self.n, e1, self.tol, e2, b2))
         assert e1 <= self.tol and e2 <= b2, (what, e1, self.tol, e2, b2)
-
-
-def expected_topn(mean, sd, rated, topn, risk, exclude):
-    key = mean - risk * sd
-    item = np.arange(len(mean))
-    if exclude:
-        keep = np.ones(len(mean), bool)
-        keep[rated.astype(np.int64)] = False
-        item, key = item[keep], key[keep]
-    order = item[np.lexsort((item, -key))][:topn]
-    out = np.full(topn, -1, np.int64)
-    out[:len(order)] = order
-    return out
 
 
 @pytest.fixture(scope="module")

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import write_m1m100k_libfm
+from sample_files import expected_topn  # the selection's order: one copy for the list tests
 from sbmf import (SBMF_E_ARG, SBMF_E_STATE, Data, FMLearnSBPMF, SBMFError, device_usage, synth)
 from sbmf._lib import CLI_PATH
 
@@ -154,19 +155,6 @@ def test_agrees_with_predict(ml100k, quirks):
 
 
 # ---- 4. selection
-def expected_topn(mean, sd, rated, topn, risk, exclude):
-    key = mean - risk * sd
-    item = np.arange(len(mean))
-    if exclude:
-        keep = np.ones(len(mean), bool)
-        keep[rated] = False
-        item, key = item[keep], key[keep]
-    order = item[np.lexsort((item, -key))][:topn]
-    out = np.full(topn, -1, np.int64)
-    out[:len(order)] = order
-    return out
-
-
 def check_selection(L, users, tr, topn, risk, exclude):
     items, mean, sd = L.recommend(topn=topn, exclude_rated=exclude, risk=risk)
     assert items.shape == mean.shape == sd.shape == (len(users), topn) and items.dtype == np.int64

@@ -23,6 +23,8 @@ import sbmf
 from sbmf import SBMF_E_ARG, SBMF_E_STATE, Communicator, Data, FMLearnSBPMF, SBMFError, device_usage, synth
 from sbmf._lib import CLI_PATH, lib
 
+from sample_files import expected_topn  # the selection's order: one copy for the list tests
+
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -52
@@ -259,19 +261,6 @@ def test_more_users_than_one_slice_and_the_per_sample_loop(ml100k):
 
 
 # ---- 6. selection
-def expected_topn(mean, sd, rated, topn, risk, exclude):
-    key = mean - risk * sd
-    item = np.arange(len(mean))
-    if exclude:
-        keep = np.ones(len(mean), bool)
-        keep[rated] = False
-        item, key = item[keep], key[keep]
-    order = item[np.lexsort((item, -key))][:topn]
-    out = np.full(topn, -1, np.int64)
-    out[:len(order)] = order
-    return out
-
-
 @pytest.fixture(scope="module")
 def store37(ml100k):
     tr, _ = ml100k
