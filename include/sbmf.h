@@ -969,6 +969,83 @@ int sbmf_test_samples_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
  * the default, one launch per sample and scan (the faster form on the device: DESIGN.md 4.8). */
 int sbmf_test_samples_tune(sbmf_ctx* ctx, uint64_t budget_bytes, int unfused);
 
+/* --- online VB: the posterior, closed-form top-N for users and guests, a model file ---------- */
+/* Not a reference interface.  The online VB learner (SBMF_METHOD_VB) keeps a
+ * Gaussian mean and variance for the global bias, every bias and every factor,
+ * so the moments of a score need no sampling.  With user u's and item j's means
+ * m, variances s (biases: w) and the global bias (m0, s0):
+ *   d    = sum_f m_uf m_jf
+ *   tv   = sum_f (s_uf s_jf + s_uf m_jf^2 + s_jf m_uf^2)
+ *   mean = ((d + m^w_u) + m^w_j) + m0        var = ((tv + s^w_u) + s^w_j) + s0
+ * stdev = sqrt(var).  These are the moments of the model's prediction: no clamp
+ * (the moments of a clamped product are not closed-form) and no 1 / alpha noise
+ * term.  Every call below answers from the context's current state -- before any
+ * epoch, the initial one -- and leaves training untouched: an epoch after it is
+ * bit-identical to one without it.
+ * SBMF_E_STATE: a context that does not run the online VB learner, that joined a
+ * communicator or is a virtual rank, or is not prepared.  SBMF_E_ARG: topn
+ * outside 1..1024, scans outside 1..64, an id out of range, flags other than
+ * bit 0 (keep rated items; a clamp bit is refused). */
+/* The posterior itself; any pointer may be NULL.  U_* [num_users][K], V_*
+ * [num_items][K], bu_* [num_users], bv_* [num_items], b0 = {mean, variance},
+ * hyper [K + 3] = alpha, sigma_0, sigma_w, sigma_v[K]. */
+int sbmf_vb_get_posterior(sbmf_ctx* ctx, double* U_mean, double* U_var, double* V_mean, double* V_var, double* bu_mean,
+                          double* bu_var, double* bv_mean, double* bv_var, double* b0, double* hyper);
+/* One user's full row: mean[j], stdev[j] for j < num_items (stdev may be NULL). */
+int sbmf_vb_scores(sbmf_ctx* ctx, uint32_t user, double* mean, double* stdev);
+/* Per named user (repeats allowed) the topn items with the largest
+ * mean - risk * stdev, ties by ascending item id, the user's train items left
+ * out unless flags bit 0 is set; outputs [n][topn], slots past the candidates
+ * hold item 0xffffffff and NaN.  Lists longer than a device budget are served
+ * in slices, with the same result. */
+int sbmf_vb_recommend(sbmf_ctx* ctx, uint32_t n, const uint32_t* users, uint32_t topn, uint32_t flags, double risk,
+                      uint32_t* items, double* mean, double* stdev);
+/* mean[q], stdev[q] of the pairs (users[q], items[q]). */
+int sbmf_vb_predict(sbmf_ctx* ctx, uint64_t n, const uint32_t* users, const uint32_t* items, double* mean, double* stdev);
+/* Guests given by their ratings, the CSR of sbmf_foldin_users.  A guest's
+ * posterior, items, m0 and alpha held fixed, is the learner's update_w then
+ * update_v (factor-outer) at step size 1: with n ratings (j, r_j),
+ *   P_b = sigma_w + alpha n,  P_f = sigma_v[f] + alpha sum_j (m_jf^2 + s_jf),
+ * from b = 0, g = 0, e_j = r_j - m0 - m^w_j, `scans` (1..64) times
+ *   b   <- alpha sum_j (e_j + b) / P_b;               e_j -= delta b
+ *   g_f <- alpha sum_j m_jf (e_j + g_f m_jf) / P_f;    e_j -= m_jf delta g_f   (f in order)
+ * and variances 1 / P_b, 1 / P_f.  A guest without ratings gets the prior.
+ * Outputs row_mean, row_var [n][K], b_mean, b_var [n]; any may be NULL. */
+int sbmf_vb_foldin_rows(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                        uint32_t scans, double* row_mean, double* row_var, double* b_mean, double* b_var);
+/* One guest's (its `len` items and ratings) full row, as sbmf_vb_scores. */
+int sbmf_vb_foldin_scores(sbmf_ctx* ctx, uint32_t len, const uint32_t* items, const double* ratings, uint32_t scans,
+                          double* mean, double* stdev);
+/* sbmf_vb_recommend for guests; "rated" items are the guest's own. */
+int sbmf_vb_foldin_recommend(sbmf_ctx* ctx, uint32_t n, const uint32_t* ptr, const uint32_t* items, const double* ratings,
+                             uint32_t scans, uint32_t topn, uint32_t flags, double risk, uint32_t* out_items, double* mean,
+                             double* stdev);
+/* The posterior as a file (little-endian): magic "SBMFVBP1", uint32 version (1),
+ * num_users, num_items, K; then float64 m0, s0, alpha, sigma_0, sigma_w,
+ * sigma_v[K]; then float64 arrays in sbmf_vb_get_posterior's order: U_mean,
+ * U_var, V_mean, V_var, bu_mean, bu_var, bv_mean, bv_var.
+ * bytes = 24 + 8 (5 + K) + 16 (K + 1) (num_users + num_items).
+ * load needs a prepared VB context of the same dims and replaces its means and
+ * variances; sbmf_run on that context is then SBMF_E_STATE (the file holds no
+ * natural parameters or step counts).  A file that cannot be opened, a bad
+ * magic, an unknown version, a truncated file or trailing bytes: SBMF_E_IO;
+ * other dims than the context's: SBMF_E_ARG; either way nothing is loaded. */
+int sbmf_vb_save_posterior(sbmf_ctx* ctx, const char* path);
+int sbmf_vb_load_posterior(sbmf_ctx* ctx, const char* path);
+/* Reads and validates a file's header alone (no context, no GPU). */
+int sbmf_vb_posterior_file_info(const char* path, uint32_t* version, uint32_t* num_users, uint32_t* num_items,
+                                uint32_t* num_factor, uint64_t* bytes);
+/* Device time (HIP events), ms, of the last transpose of the tables (made by the
+ * first call after an epoch or a load), scoring launch, selection and guest
+ * launch; 0 before the first. */
+int sbmf_vb_timing(sbmf_ctx* ctx, double* ms_transpose, double* ms_score, double* ms_select, double* ms_guest);
+/* Test hooks: one user's mean[j] and variance[j] as the scoring kernel wrote
+ * them; the temporaries' budget of the lists in bytes (0: the default); the
+ * scoring launch's rows per workgroup and LDS bytes at Kp. */
+int sbmf_test_vb_moments(sbmf_ctx* ctx, uint32_t user, double* mean, double* var);
+int sbmf_test_vb_tune(sbmf_ctx* ctx, uint64_t budget_bytes);
+int sbmf_test_vb_score_lds(uint32_t Kp, uint32_t* rows, uint64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #include "samples.h"
 #include "samples_foldin.h"
 #include "vbo.h"
+#include "vb_lists.h"
 
 struct sbmf_ctx;
 
@@ -153,6 +154,23 @@ struct SampleStore {
     void drop();
     template <typename T>
     void keep(sbmf_ctx* c, const Hyper& hy, hipStream_t se);  // this sweep's tables into the next slot, if it is one to keep
+};
+
+// The online VB learner's lists (sbmf_vb_*, vb_lists.cpp): nothing is kept between calls but the
+// user-side CSR of the train set (the rated-item masks; built at the first call that needs it)
+// and the event pairs of the last transpose, scoring, selection and guest launch.  Nothing here
+// exists before the first call.
+struct VBLists {
+    DBuf d_uptr, d_upart;
+    bool csr = false, spans = false;
+    Span tr, sc, sel, gu;
+    uint64_t budget = 0;  // test hook (sbmf_test_vb_tune): the temporaries' budget in bytes (0: the default)
+    void drop() {
+        d_uptr.release();
+        d_upart.release();
+        for (Span* s : {&tr, &sc, &sel, &gu}) s->destroy();
+        csr = spans = false;
+    }
 };
 
 struct sbmf_ctx {
@@ -300,6 +318,7 @@ struct sbmf_ctx {
     FMQueryList fmqd;
     SampleStore samples;
     VBLearner* vb = nullptr;  // -method vb (vbo.cpp)
+    VBLists vbl;
     // -method mcmc --order libfm / als: libFM's chain (fmc.cpp) on triples (fmm.cpp) or on cases
     // with any number of features (fmg.cpp).  ctr / cte: the host copies of sbmf_set_train_cases /
     // sbmf_set_test_cases (or, with SBMF_FMM_GENERAL=1, the triples of sbmf_set_train restated

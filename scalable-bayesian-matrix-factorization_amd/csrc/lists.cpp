@@ -40,7 +40,7 @@ void TopnScratch::alloc(uint32_t rows, uint32_t topn, uint32_t J, bool exclude) 
 }
 void select_topn(TopnScratch& t, const uint32_t* d_ids, uint32_t m, const double* S1, const double* S2, uint32_t J,
                  uint32_t count, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn, double risk, Span& span,
-                 hipStream_t st, uint32_t* items, double* mean, double* stdev) {
+                 hipStream_t st, uint32_t* items, double* mean, double* stdev, bool given) {
     const uint32_t Jw = watch_jw(J);
     const size_t slots = (size_t)m * topn;
     uint32_t* mask = csr_ptr ? t.d_mask.as<uint32_t>() : nullptr;
@@ -50,7 +50,8 @@ void select_topn(TopnScratch& t, const uint32_t* d_ids, uint32_t m, const double
         HIPCHK(hipMemsetAsync(mask, 0, (size_t)m * Jw * sizeof(uint32_t), st));
         HIPCHK(launch_watch_mask(d_ids, m, csr_ptr, csr_items, mask, Jw, st));
     }
-    HIPCHK(launch_watch_select(m, S1, S2, J, (double)count, risk, mask, topn, t.d_it.as<uint32_t>(), ms, ms + slots, st));
+    if (given) HIPCHK(launch_watch_select_given(m, S1, S2, J, risk, mask, topn, t.d_it.as<uint32_t>(), ms, ms + slots, st));
+    else HIPCHK(launch_watch_select(m, S1, S2, J, (double)count, risk, mask, topn, t.d_it.as<uint32_t>(), ms, ms + slots, st));
     span.end(st);
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(items, t.d_it.p, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));

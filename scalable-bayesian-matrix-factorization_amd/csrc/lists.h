@@ -24,9 +24,10 @@ struct TopnScratch {
 // Top-N of the m rows whose sums S1 / S2 [m][Jp] hold `count` samples: mask (the columns
 // csr_items[csr_ptr[i] .. csr_ptr[i + 1]) of row d_ids[r] = i are left out; a null csr_ptr: none
 // is), select, synchronise, download into items / mean / stdev [m][topn] (stdev may be null).
+// given: S1 / S2 hold the rows' means and variances themselves (the online VB lists; count unused).
 void select_topn(TopnScratch& t, const uint32_t* d_ids, uint32_t m, const double* S1, const double* S2, uint32_t J,
                  uint32_t count, const uint32_t* csr_ptr, const uint32_t* csr_items, uint32_t topn, double risk, Span& span,
-                 hipStream_t st, uint32_t* items, double* mean, double* stdev);
+                 hipStream_t st, uint32_t* items, double* mean, double* stdev, bool given = false);
 // mean and (may be null) spread [J] of one row of sums S1 / S2 over `count` samples
 void row_moments(const double* S1, const double* S2, uint32_t J, uint32_t count, hipStream_t st, double* mean, double* stdev);
 

@@ -57,4 +57,10 @@ hipError_t launch_watch_select(uint32_t n, const double* S1, const double* S2, u
                                const uint32_t* mask, uint32_t topn, uint32_t* items, double* mean, double* sd,
                                hipStream_t st);
 
+// The same selection over rows that hold a mean and a variance themselves (M, Vr [n][Jp]): sd =
+// sqrt(max(0, var)), no division and no difference of squares (the online VB lists, vb_lists.h).
+hipError_t launch_watch_select_given(uint32_t n, const double* M, const double* Vr, uint32_t J, double risk,
+                                     const uint32_t* mask, uint32_t topn, uint32_t* items, double* mean, double* sd,
+                                     hipStream_t st);
+
 }  // namespace sbmf

@@ -216,9 +216,10 @@ hipError_t launch_watch_mask(const uint32_t* users, uint32_t n, const uint32_t* 
 // and a scan from the top bin for the one that holds rank `rem`.  The elements at or above the
 // threshold -- exactly topn of them, or every candidate if there are fewer -- go to LDS and
 // are put in order by a bitonic sort of 1024 slots; empty slots (key 0, item all ones) sort last.
+// GIVEN: the two rows are a mean and a variance (watch_given_moments), not sums over nw samples.
 constexpr int WATCH_P = 32;
 
-template <bool CACHED>
+template <bool CACHED, bool GIVEN = false>
 __global__ __launch_bounds__(1024) void k_watch_select(const double* __restrict__ S1, const double* __restrict__ S2,
                                                        uint32_t Jp, uint32_t J, double nw, double risk,
                                                        const uint32_t* __restrict__ mask, uint32_t Jw, uint32_t topn,
@@ -231,7 +232,8 @@ __global__ __launch_bounds__(1024) void k_watch_select(const double* __restrict_
     auto key_of = [&](uint32_t item) -> uint64_t {
         if (mk && ((mk[item >> 5] >> (item & 31)) & 1u)) return 0;
         double m, sd;
-        watch_moments(s1[item], s2[item], nw, m, sd);
+        if constexpr (GIVEN) watch_given_moments(s1[item], s2[item], m, sd);
+        else watch_moments(s1[item], s2[item], nw, m, sd);
         return watch_key(m, sd, risk);
     };
     uint64_t kreg[CACHED ? WATCH_P : 1];
@@ -332,7 +334,10 @@ __global__ __launch_bounds__(1024) void k_watch_select(const double* __restrict_
     if (tid < topn) {
         const uint32_t it = sitem[tid];
         double m = NAN, sd = NAN;
-        if (it != 0xffffffffu) watch_moments(s1[it], s2[it], nw, m, sd);
+        if (it != 0xffffffffu) {
+            if constexpr (GIVEN) watch_given_moments(s1[it], s2[it], m, sd);
+            else watch_moments(s1[it], s2[it], nw, m, sd);
+        }
         const size_t o = (size_t)blockIdx.x * topn + tid;
         out_items[o] = it;
         out_mean[o] = m;
@@ -350,6 +355,19 @@ hipError_t launch_watch_select(uint32_t n, const double* S1, const double* S2, u
         k_watch_select<true><<<n, 1024, 0, st>>>(S1, S2, Jp, J, nw, risk, mask, Jw, topn, items, mean, sd);
     else
         k_watch_select<false><<<n, 1024, 0, st>>>(S1, S2, Jp, J, nw, risk, mask, Jw, topn, items, mean, sd);
+    return hipGetLastError();
+}
+
+hipError_t launch_watch_select_given(uint32_t n, const double* M, const double* Vr, uint32_t J, double risk,
+                                     const uint32_t* mask, uint32_t topn, uint32_t* items, double* mean, double* sd,
+                                     hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (topn == 0 || topn > 1024) return hipErrorInvalidValue;
+    const uint32_t Jp = watch_jp(J), Jw = watch_jw(J);
+    if (J <= (uint32_t)WATCH_P * 1024)
+        k_watch_select<true, true><<<n, 1024, 0, st>>>(M, Vr, Jp, J, 1.0, risk, mask, Jw, topn, items, mean, sd);
+    else
+        k_watch_select<false, true><<<n, 1024, 0, st>>>(M, Vr, Jp, J, 1.0, risk, mask, Jw, topn, items, mean, sd);
     return hipGetLastError();
 }
 

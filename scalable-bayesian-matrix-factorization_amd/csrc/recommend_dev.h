@@ -78,5 +78,13 @@ __device__ __forceinline__ void watch_moments(double s1, double s2, double nw, d
     const double v = s2 / nw - mm;
     sd = sqrt(v > 0.0 ? v : 0.0);
 }
+// The same pair when the two rows ARE a mean and a variance (the online VB lists, vb_lists.hip:
+// closed-form moments, no sums): s2 / nw - mean^2 of var + mean^2 would cancel to 0 wherever
+// var << mean^2, the normal case of a converged posterior.
+__device__ __forceinline__ void watch_given_moments(double m, double var, double& mean, double& sd) {
+#pragma clang fp contract(off)
+    mean = m;
+    sd = sqrt(var > 0.0 ? var : 0.0);
+}
 
 }  // namespace sbmf

@@ -49,6 +49,7 @@ sbmf_ctx::~sbmf_ctx() {
     for (ScoreList* l : {&watch, &guests, &fmq}) l->drop();
     fmqd.drop();
     samples.drop();
+    vbl.drop();
     pinned_free(h_fhyp, h_fhyp_bytes);
     event_destroy(hev);
     stream_destroy(sto);
@@ -789,6 +790,9 @@ int sbmf_run(sbmf_ctx* ctx, uint32_t sweeps, sbmf_sweep_cb cb, void* user) {
     HIPCHK(hipSetDevice(ctx->cfg.device));
     if (!ctx->prepared) prepare_ctx(ctx);
     if (ctx->vb) {
+        if (vbo_loaded(ctx->vb))
+            sbmf::fail(SBMF_E_STATE, "sbmf_run: this context's posterior came from a file (sbmf_vb_load_posterior), which "
+                                     "holds no natural parameters or step counts: training cannot resume from it");
         vbo_run(ctx->vb, sweeps, cb, user);
         ctx->timing = sbmf_timing{};
         ctx->timing.n_launch = vbo_launches(ctx->vb);

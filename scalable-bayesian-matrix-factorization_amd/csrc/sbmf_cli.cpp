@@ -508,6 +508,21 @@ void register_flags(CmdLine& cl) {
                                        "-recommend_guests numbers");
     cl.reg("samples_scans", "coordinate scans of a guest's row per stored sample, 1..64; default=1 [with "
                             "-samples_recommend_guests]");
+    // the online VB learner's closed-form lists and model file (sbmf_vb_recommend / sbmf_vb_foldin_recommend / sbmf_vb_save_posterior)
+    cl.reg("vb_recommend", "filename for output: per user of -vb_users the -vb_topn unrated items with the largest posterior "
+                           "mean score (less -vb_risk stdevs) under the online VB posterior, in closed form, -recommend's "
+                           "lines; -method vb only");
+    cl.reg("vb_users", "filename with one user id per line [MANDATORY with -vb_recommend]");
+    cl.reg("vb_recommend_guests", "filename for output: the same lists for the guests of -vb_guests, each guest's posterior "
+                                  "from its ratings with the items held fixed; -method vb only");
+    cl.reg("vb_guests", "filename in -rec_guests' format ('guest item rating' per line) [MANDATORY with -vb_recommend_guests]");
+    cl.reg("vb_topn", "items per user or guest, 1..1024; default=10 [with -vb_recommend / -vb_recommend_guests]");
+    cl.reg("vb_risk", "rank by mean - x * stdev; default=0 [with -vb_recommend / -vb_recommend_guests]");
+    cl.reg("vb_scans", "coordinate scans of a guest's posterior, 1..64; default=1 [with -vb_recommend_guests]");
+    cl.reg("vb_model_out", "filename for output: the posterior means and variances after the run; -method vb only");
+    cl.reg("vb_model_in", "filename of a -vb_model_out file: no epoch is run; prints '#Model<TAB>Test=<rmse>' of the clamped "
+                          "posterior-mean prediction of the -test pairs, writes -out from it and serves -vb_recommend / "
+                          "-vb_recommend_guests from the file; the data and -dim must be those of the run that wrote it");
     cl.reg("rec_exclude", "filename with one 'query row' line per block row left out of a query's list, the query "
                           "numbers non-decreasing");
 }
@@ -528,6 +543,9 @@ struct Options {
     std::string samples_out, samples_in;  // the sample store: written after the run | served from, without one
     std::string samples_hyper_out, samples_hyper_in;  // its hyperparameters' companion file
     long samples_scans = 1;
+    ListOpt vbusers, vbguests;  // -vb_recommend / -vb_users, -vb_recommend_guests / -vb_guests: the online VB learner's lists
+    std::string vb_model_out, vb_model_in;  // its posterior file: written after the run | served from, without one
+    long vb_scans = 1;
     long samples_every = 1, samples_max = 0;  // (0: every kept sweep of the run)
     long topn = 10;  // -rec_topn and -rec_risk, shared by the three
     double risk = 0.0;
@@ -631,6 +649,35 @@ void resolve_flags(const CmdLine& cl, Options& o) {
     if (sg.on && sg.in.empty()) fail("-samples_recommend_guests needs -samples_guests <file> ('guest item rating' per line)");
     o.samples_scans = cl.getl("samples_scans", 1);
     if (cl.has("samples_scans") && (o.samples_scans < 1 || o.samples_scans > 64)) fail("-samples_scans must be in 1..64");
+    // the online VB learner's lists and model file: -method vb, then each flag with its partner
+    for (const char* f : {"vb_recommend", "vb_users", "vb_recommend_guests", "vb_guests", "vb_topn", "vb_risk", "vb_scans",
+                          "vb_model_out", "vb_model_in"})
+        if (cl.has(f) && !o.vb) fail(std::string("-") + f + " is offered by the online VB learner: use -method vb");
+    ListOpt &vu = o.vbusers, &vg = o.vbguests;
+    vu = {cl.has("vb_recommend"), cl.get("vb_users", ""), cl.get("vb_recommend", "")};
+    vg = {cl.has("vb_recommend_guests"), cl.get("vb_guests", ""), cl.get("vb_recommend_guests", "")};
+    if (vu.on && vu.out.empty()) fail("-vb_recommend needs a file name");
+    if (vu.on && vu.in.empty()) fail("-vb_recommend needs -vb_users <file> (one user id per line)");
+    if (!vu.on && cl.has("vb_users")) fail("-vb_users goes with -vb_recommend <file>");
+    if (vg.on && vg.out.empty()) fail("-vb_recommend_guests needs a file name");
+    if (vg.on && vg.in.empty()) fail("-vb_recommend_guests needs -vb_guests <file> ('guest item rating' per line)");
+    if (!vg.on && cl.has("vb_guests")) fail("-vb_guests goes with -vb_recommend_guests <file>");
+    if (!vg.on && cl.has("vb_scans")) fail("-vb_scans goes with -vb_recommend_guests <file>");
+    if (!vu.on && !vg.on && (cl.has("vb_topn") || cl.has("vb_risk")))
+        fail("-vb_topn / -vb_risk go with -vb_recommend or -vb_recommend_guests");
+    if (vu.on || vg.on) {  // (-rec_topn / -rec_risk have no list with -method vb: the top-N writer's pair is this one)
+        o.topn = cl.getl("vb_topn", 10);
+        o.risk = cl.getd("vb_risk", 0.0);
+        if (o.topn < 1 || o.topn > 1024) fail("-vb_topn must be in 1..1024");
+    }
+    o.vb_scans = cl.getl("vb_scans", 1);
+    if (cl.has("vb_scans") && (o.vb_scans < 1 || o.vb_scans > 64)) fail("-vb_scans must be in 1..64");
+    o.vb_model_out = cl.get("vb_model_out", "");
+    o.vb_model_in = cl.get("vb_model_in", "");
+    if (cl.has("vb_model_out") && o.vb_model_out.empty()) fail("-vb_model_out needs a file name");
+    if (cl.has("vb_model_in") && o.vb_model_in.empty()) fail("-vb_model_in needs a file name");
+    if (cl.has("vb_model_in") && (cl.has("vb_model_out") || cl.has("rlog")))
+        fail("-vb_model_in runs no epoch: it does not go with -vb_model_out or -rlog");
 }
 
 // Step 2: what also depends on the kind of input, for which -format auto looks into the train file (the first
@@ -850,12 +897,16 @@ void load_data(Options& o, HostData& d) {
 // The list files, all parsed before the context is created.  The guests come after load_data has settled the item
 // offset: their item ids come in the id space -recommend prints (on libFM input the feature id).
 void load_lists(const Options& o, HostData& d) {
-    if (o.users.on) d.rec_ids = read_ids(o.users.in, "-rec_users", "user id");
-    if (o.users.on && d.rec_ids.empty()) fail("-rec_users: " + o.users.in + " lists no user");
-    // (-recommend_guests and -samples_recommend_guests never meet: the second goes with -samples_in)
-    const ListOpt& gl = o.sguests.on ? o.sguests : o.guests;
+    // (-recommend and -vb_recommend never meet: the second goes with -method vb, which refuses the first)
+    const ListOpt& ul = o.vbusers.on ? o.vbusers : o.users;
+    const std::string uflag = o.vbusers.on ? "-vb_users" : "-rec_users";
+    if (ul.on) d.rec_ids = read_ids(ul.in, uflag.c_str(), "user id");
+    if (ul.on && d.rec_ids.empty()) fail(uflag + ": " + ul.in + " lists no user");
+    // (-recommend_guests, -samples_recommend_guests and -vb_recommend_guests never meet: the second goes with
+    // -samples_in, the third with -method vb)
+    const ListOpt& gl = o.sguests.on ? o.sguests : o.vbguests.on ? o.vbguests : o.guests;
     if (gl.on) {
-        const std::string flag = o.sguests.on ? "-samples_guests" : "-rec_guests";
+        const std::string flag = o.sguests.on ? "-samples_guests" : o.vbguests.on ? "-vb_guests" : "-rec_guests";
         unsigned long long it = 0;
         double r = 0.0;
         d.guests = read_grouped(
@@ -1023,11 +1074,31 @@ void write_topn(sbmf_ctx* ctx, Recommend recommend, const Options& o, const std:
     std::fclose(f);
 }
 
+// -vb_recommend and -vb_recommend_guests: the online VB posterior's lists through the top-N writer
+void write_vb_lists(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    if (o.vbusers.on) {
+        const uint32_t nu = (uint32_t)d.rec_ids.size();
+        const uint32_t* ids = d.rec_ids.data();
+        write_topn(ctx, [&](sbmf_ctx* c, uint32_t topn, uint32_t flags, double risk, uint32_t* it, double* mean, double* sd) {
+            return sbmf_vb_recommend(c, nu, ids, topn, flags, risk, it, mean, sd);
+        }, o, o.vbusers.out, nu, ids, d.ioff);
+    }
+    if (o.vbguests.on) {
+        const uint32_t ng = (uint32_t)d.guests.ptr.size() - 1, scans = (uint32_t)o.vb_scans;
+        write_topn(ctx, [&](sbmf_ctx* c, uint32_t topn, uint32_t flags, double risk, uint32_t* it, double* mean, double* sd) {
+            return sbmf_vb_foldin_recommend(c, ng, d.guests.ptr.data(), d.guests.val.data(), d.g_ratings.data(), scans, topn,
+                                            flags, risk, it, mean, sd);
+        }, o, o.vbguests.out, ng, nullptr, d.ioff);
+    }
+}
+
 void write_outputs(sbmf_ctx* ctx, const Options& o, const HostData& d) {
     // queries, then users, then guests; ids as in the input files: on libFM input the item's feature id
     if (o.queries.on) write_topn(ctx, sbmf_fm_query_recommend, o, o.queries.out, d.qcases.n, nullptr, 0);
     if (o.users.on) write_topn(ctx, sbmf_recommend, o, o.users.out, d.rec_ids.size(), d.rec_ids.data(), d.ioff);
     if (o.guests.on) write_topn(ctx, sbmf_foldin_recommend, o, o.guests.out, d.guests.ptr.size() - 1, nullptr, d.ioff);
+    write_vb_lists(ctx, o, d);
+    if (!o.vb_model_out.empty()) chk(ctx, sbmf_vb_save_posterior(ctx, o.vb_model_out.c_str()));
     if (!o.out.empty()) {
         uint64_t nte = 0;
         chk(ctx, sbmf_get_dims(ctx, nullptr, nullptr, nullptr, &nte));
@@ -1073,6 +1144,28 @@ void serve_samples(sbmf_ctx* ctx, const Options& o, const HostData& d) {
     }
 }
 
+// -vb_model_in: no epoch.  The file's posterior-mean prediction of the test pairs, clamped to the train targets'
+// range as the learner's own, its RMSE on the "#Model" line, -out from it, and the lists from the file.
+void serve_vb_model(sbmf_ctx* ctx, const Options& o, const HostData& d) {
+    chk(ctx, sbmf_vb_load_posterior(ctx, o.vb_model_in.c_str()));
+    const uint64_t n = d.te.n;
+    std::vector<double> pred(n);
+    chk(ctx, sbmf_vb_predict(ctx, n, d.te.user, d.te.item, pred.data(), nullptr));
+    float lo = 3.402823466e+38f, hi = -3.402823466e+38f;  // the learner's range: the train targets as floats (vbo.cpp)
+    for (uint64_t x = 0; x < d.tr.n; ++x) lo = std::min(lo, (float)d.tr.rating[x]), hi = std::max(hi, (float)d.tr.rating[x]);
+    double se = 0.0;
+    for (uint64_t t = 0; t < n; ++t) {
+        pred[t] = std::min<double>(std::max<double>(pred[t], lo), hi);
+        se += (pred[t] - d.te.rating[t]) * (pred[t] - d.te.rating[t]);
+    }
+    std::cout << "#Model\tTest=" << (n ? std::sqrt(se / (double)n) : std::numeric_limits<double>::quiet_NaN()) << std::endl;
+    write_vb_lists(ctx, o, d);
+    if (!o.out.empty()) {
+        std::ofstream out(o.out);
+        for (double p : pred) out << p << "\n";
+    }
+}
+
 // SBMF_EXIT=guard (opt-in; round 3's default): leave through sbmf_exit_guard's
 // handler (registered at main's start, before the first HIP call), so a profiler's
 // exit handlers still run and the shared-library finalizers do not.  The finalizer
@@ -1111,6 +1204,8 @@ int main(int argc, char** argv) {
         print_dims(ctx, o, d);
         if (!o.samples_in.empty()) {
             serve_samples(ctx, o, d);
+        } else if (!o.vb_model_in.empty()) {
+            serve_vb_model(ctx, o, d);
         } else {
             run(ctx, o, d);
             write_outputs(ctx, o, d);

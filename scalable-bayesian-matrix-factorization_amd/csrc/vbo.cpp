@@ -114,6 +114,8 @@ struct VBLearner {
     std::vector<hipEvent_t> fev;
     double ms_factor_sum = 0.0;  // the last run's epochs: factor-pass time summed ...
     uint32_t n_factor_epochs = 0;  // ... over this many epochs
+    // the lists (vb_lists.cpp): d_muT / d_sgT hold the current tables' transposes; a posterior file was loaded
+    bool T_fresh = false, loaded = false;
 
     ~VBLearner() {
         if (worker.joinable()) worker.join();
@@ -657,6 +659,7 @@ void VBLearner::stage_layout(VBLayout& L, uint32_t e) {
 }
 
 void VBLearner::run(uint32_t epochs, sbmf_sweep_cb cb, void* user) {
+    T_fresh = false;
     for (uint32_t it = 0; it < epochs; ++it) {
         const auto h0 = std::chrono::steady_clock::now();
         // this epoch's layout: built and uploaded by the worker during the previous epoch
@@ -858,6 +861,22 @@ void vbo_hyper_out(VBLearner* L, double* h4k, double* alpha) {
         *alpha = sc.alpha;
     }
 }
+VBView vbo_view(VBLearner* L) {
+    return VBView{L->tb, L->d_muT.as<double>(), L->d_sgT.as<double>(), L->K, L->Kp, L->I, L->J, L->st};
+}
+bool vbo_fresh_transposes(VBLearner* L) {
+    if (L->T_fresh) return false;
+    HIPCHK(vbo_transpose(L->tb.mu_v, L->d_muT.as<double>(), L->K, L->Kp, L->p, L->st));
+    HIPCHK(vbo_transpose(L->tb.sg_v, L->d_sgT.as<double>(), L->K, L->Kp, L->p, L->st));
+    L->T_fresh = true;
+    return true;
+}
+void vbo_set_loaded(VBLearner* L) {
+    L->loaded = true;
+    L->T_fresh = false;
+}
+bool vbo_loaded(const VBLearner* L) { return L->loaded; }
+bool vbo_transposes_fresh(const VBLearner* L) { return L->T_fresh; }
 double vbo_layout_ms(const VBLearner* L) { return L->ms_layout; }
 uint32_t vbo_launches(const VBLearner* L) { return L->n_launch; }
 double vbo_factor_ms(const VBLearner* L) { return L->n_factor_epochs ? L->ms_factor_sum / L->n_factor_epochs : 0.0; }

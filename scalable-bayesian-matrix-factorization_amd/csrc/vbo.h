@@ -148,6 +148,24 @@ uint32_t vbo_launches(const VBLearner* L);
 // HIP events around each batch's factor loop), averaged over the last vbo_run's epochs
 double vbo_factor_ms(const VBLearner* L);
 
+// ---- the lists' view of the learner (vb_lists.cpp): the tables and scalars on the device, the
+// attribute-major transposes [p][Kp] and the learner's stream
+struct VBView {
+    VBTables tb;
+    double *muT, *sgT;
+    uint32_t K, Kp, I, J;
+    hipStream_t st;
+};
+VBView vbo_view(VBLearner* L);
+// muT / sgT are the current tables' transposes: built here (queued on the stream) unless they
+// still are -- vbo_run and vbo_set_loaded invalidate them; returns whether it transposed
+bool vbo_fresh_transposes(VBLearner* L);
+bool vbo_transposes_fresh(const VBLearner* L);
+// a posterior file replaced the means and variances (sbmf_vb_load_posterior): the natural
+// parameters and step counts no longer belong to them, and sbmf_run is refused
+void vbo_set_loaded(VBLearner* L);
+bool vbo_loaded(const VBLearner* L);
+
 // scratch doubles vbo_update_w0 / vbo_hyper (one rank) and vbo_hyper_local /
 // vbo_hyper_final (several ranks) need for B cases:
 //   vbo_hyper:       [alpha partials nab | 8 | sig partials (K+1) x nchunk(p)]

@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import (F32, F64, METHOD_ALS, METHOD_LIBFM_MCMC, METHOD_MCMC, METHOD_VB, QUIRKS_BIAS2, QUIRKS_BIAS22, QUIRKS_FINAL, QUIRKS_NONE, QUIRKS_SBPMF2, RNG_PHILOX, RNG_REFERENCE, SBMF_E_ARG,
                    SBMF_E_COMM, SBMF_E_DEVICE, SBMF_E_IO, SBMF_E_NOMEM, SBMF_E_STATE, SBMF_OK)
 
-__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "samples_file_info", "samples_hyper_file_info", "Communicator", "save_triples", "config_default",
+__all__ = ["FMLearnSBPMF", "FMLearnVBOnline", "Data", "Cases", "Relation", "load_libfm_relation", "save_libfm_relation", "load_libfm_cases", "load_libfm_meta", "parse_regular", "fm_ranges", "SBMFError", "load_triples", "load_libfm", "load_libfm_binary", "save_libfm_binary", "libfm_binary_kind", "device_usage", "samples_file_info", "samples_hyper_file_info", "vb_posterior_file_info", "Communicator", "save_triples", "config_default",
            "RNG_REFERENCE", "RNG_PHILOX", "QUIRKS_FINAL", "QUIRKS_SBPMF2", "QUIRKS_NONE",
            "QUIRKS_BIAS2", "QUIRKS_BIAS22", "F64", "F32"]
 
@@ -878,6 +878,77 @@ class FMLearnSBPMF:
         and of the last selection."""
         return self._ms(lib.sbmf_fm_query_timing, "ms_terms", "ms_score", "ms_select")
 
+    # -- online VB: the posterior, closed-form top-N for users and guests, the model file
+    def vb_posterior(self):
+        """The online VB learner's posterior means and variances (sbmf_vb_get_posterior): a dict
+        with U_mean, U_var [users, K], V_mean, V_var [items, K], bu_mean, bu_var [users], bv_mean,
+        bv_var [items], b0 = (mean, variance), alpha, sigma_0, sigma_w and sigma_v [K]."""
+        nu, ni, _, _ = self.dims()
+        K = self.cfg.num_factor
+        shapes = (("U_mean", (nu, K)), ("U_var", (nu, K)), ("V_mean", (ni, K)), ("V_var", (ni, K)), ("bu_mean", (nu,)),
+                  ("bu_var", (nu,)), ("bv_mean", (ni,)), ("bv_var", (ni,)))
+        out = {k: np.zeros(s) for k, s in shapes}
+        b0, hy = np.zeros(2), np.zeros(K + 3)
+        self._check(lib.sbmf_vb_get_posterior(self.ctx, *[_ptr(out[k], C.c_double) for k, _ in shapes],
+                                              _ptr(b0, C.c_double), _ptr(hy, C.c_double)))
+        out.update(b0=(b0[0], b0[1]), alpha=hy[0], sigma_0=hy[1], sigma_w=hy[2], sigma_v=hy[3:].copy())
+        return out
+
+    def vb_scores(self, user):
+        """(mean, stdev) of ``user``'s score of every item under the VB posterior (closed form)."""
+        return self._scores(lib.sbmf_vb_scores, self.dims()[1], int(user))
+
+    def vb_recommend(self, users, topn=10, exclude_rated=True, risk=0.0):
+        """Per named user the ``topn`` items with the largest mean - risk * stdev under the VB
+        posterior: (items int64 [n, topn] with -1 in empty slots, mean, stdev)."""
+        users = _u32(users).ravel()
+        return self._topn(lib.sbmf_vb_recommend, len(users), topn, len(users), _ptr(users, C.c_uint32), int(topn),
+                          0 if exclude_rated else 1, float(risk))
+
+    def vb_predict(self, users, items):
+        """(mean, stdev) of the pairs (users[p], items[p]) under the VB posterior; no clamp."""
+        users, items = _u32(users).ravel(), _u32(items).ravel()
+        if len(users) != len(items):
+            raise ValueError("users and items must have the same length")
+        return self._scores(lib.sbmf_vb_predict, len(users), len(users), _ptr(users, C.c_uint32), _ptr(items, C.c_uint32))
+
+    def vb_foldin_rows(self, guests, scans=1):
+        """The guests' posterior (the form ``foldin`` takes), items held fixed, after ``scans``
+        coordinate scans: (row_mean [n, K], row_var [n, K], b_mean [n], b_var [n])."""
+        n, ptr, items, ratings = _guest_csr(guests)
+        K = self.cfg.num_factor
+        rm, rv, bm, bv = np.zeros((max(n, 1), K)), np.zeros((max(n, 1), K)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        self._check(lib.sbmf_vb_foldin_rows(self.ctx, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                                            _ptr(ratings, C.c_double), int(scans), _ptr(rm, C.c_double),
+                                            _ptr(rv, C.c_double), _ptr(bm, C.c_double), _ptr(bv, C.c_double)))
+        return rm[:n], rv[:n], bm[:n], bv[:n]
+
+    def vb_foldin_scores(self, items, ratings, scans=1):
+        """(mean, stdev) of one guest's score of every item under its VB posterior."""
+        items, ratings = _u32(np.asarray(items, dtype=np.int64).ravel()), _f64(np.asarray(ratings, dtype=np.float64).ravel())
+        if len(items) != len(ratings):
+            raise ValueError("items and ratings differ in length")
+        return self._scores(lib.sbmf_vb_foldin_scores, self.dims()[1], len(items), _ptr(items, C.c_uint32),
+                            _ptr(ratings, C.c_double), int(scans))
+
+    def vb_foldin_recommend(self, guests, topn=10, exclude_rated=True, risk=0.0, scans=1):
+        """``vb_recommend`` for guests named now; "rated" means the guest's own items."""
+        n, ptr, items, ratings = _guest_csr(guests)
+        return self._topn(lib.sbmf_vb_foldin_recommend, n, topn, n, _ptr(ptr, C.c_uint32), _ptr(items, C.c_uint32),
+                          _ptr(ratings, C.c_double), int(scans), int(topn), 0 if exclude_rated else 1, float(risk))
+
+    def save_vb_posterior(self, path):
+        self._check(lib.sbmf_vb_save_posterior(self.ctx, str(path).encode()))
+
+    def load_vb_posterior(self, path):
+        """Replace the posterior by a file's (a prepared VB learner of the same dims and K; no
+        epoch needed).  ``learn`` is refused afterwards: the file holds no training state."""
+        self._check(lib.sbmf_vb_load_posterior(self.ctx, str(path).encode()))
+
+    def vb_timing(self):
+        """Device ms of the last transpose of the tables, scoring launch, selection and guest launch."""
+        return self._ms(lib.sbmf_vb_timing, "ms_transpose", "ms_score", "ms_select", "ms_guest")
+
     def close(self):
         if self.ctx is not None:
             lib.sbmf_destroy(self.ctx)
@@ -914,6 +985,19 @@ def samples_file_info(path):
     out = {k: x.value for k, x in zip(keys, v)}
     out["precision"] = "f32" if out["precision"] == F32 else "f64"
     out["bias"] = bool(out["bias"])
+    out["bytes"] = b.value
+    return out
+
+
+def vb_posterior_file_info(path):
+    """sbmf_vb_posterior_file_info: a VB posterior file's header, validated against the file's size
+    (no GPU): {"version", "num_users", "num_items", "num_factor", "bytes"}."""
+    v = [C.c_uint32() for _ in range(4)]
+    b = C.c_uint64()
+    rc = lib.sbmf_vb_posterior_file_info(str(path).encode(), *[C.byref(x) for x in v], C.byref(b))
+    if rc != SBMF_OK:
+        raise SBMFError(rc, lib.sbmf_last_global_error().decode())
+    out = {k: x.value for k, x in zip(("version", "num_users", "num_items", "num_factor"), v)}
     out["bytes"] = b.value
     return out
 

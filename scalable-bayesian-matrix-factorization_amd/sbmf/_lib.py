@@ -193,6 +193,23 @@ SIGNATURES = {
     "sbmf_test_watch_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
     "sbmf_test_samples_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
     "sbmf_test_samples_tune": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int]),
+    "sbmf_vb_get_posterior": (C.c_int, [C.c_void_p] + [_P_F64] * 10),
+    "sbmf_vb_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_vb_recommend": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, C.c_uint32, C.c_uint32, C.c_double, _P_U32, _P_F64,
+                                    _P_F64]),
+    "sbmf_vb_predict": (C.c_int, [C.c_void_p, C.c_uint64, _P_U32, _P_U32, _P_F64, _P_F64]),
+    "sbmf_vb_foldin_rows": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_U32, _P_F64, C.c_uint32, _P_F64, _P_F64, _P_F64,
+                                      _P_F64]),
+    "sbmf_vb_foldin_scores": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_F64, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_vb_foldin_recommend": (C.c_int, [C.c_void_p, C.c_uint32, _P_U32, _P_U32, _P_F64, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_double, _P_U32, _P_F64, _P_F64]),
+    "sbmf_vb_save_posterior": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_vb_load_posterior": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "sbmf_vb_posterior_file_info": (C.c_int, [C.c_char_p, _P_U32, _P_U32, _P_U32, _P_U32, C.POINTER(C.c_uint64)]),
+    "sbmf_vb_timing": (C.c_int, [C.c_void_p, _P_F64, _P_F64, _P_F64, _P_F64]),
+    "sbmf_test_vb_moments": (C.c_int, [C.c_void_p, C.c_uint32, _P_F64, _P_F64]),
+    "sbmf_test_vb_tune": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "sbmf_test_vb_score_lds": (C.c_int, [C.c_uint32, _P_U32, C.POINTER(C.c_uint64)]),
 }
 
 
